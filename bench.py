@@ -5,7 +5,7 @@ cross-correlation -> argmax -> lag prior -> (x, y) grid solve), one process
 per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--engine gcc_phat|direct]
-                    [--config 2|3|4|5]
+                    [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver, N > 1)
 
 A step = one libtdoa launch over one batch of frames already resident in HBM
@@ -16,6 +16,13 @@ config 4 splits one global batch of 1e6 frames, strong scaling) and there is
 no data-path collective -- the rank logic (seeds, shard sizes, the timed
 bracket with barrier + max-over-ranks) is tdoa/shard.py, which
 tests/test_distributed.py runs with gloo.
+
+A plain run sets up, warms up, times the K steps and prints the line; with
+--dump-outputs DIR it also writes the arrays the last timed step produced
+(DIR/<name>.npy, float32 / float64; inputs are seeded, so two builds can be
+compared output for output).  Everything else the bench measures or checks
+-- `parity`, `cpu_baseline`, `gpu_clock_mhz`, config 5's `latency_ms`, config
+1's `gpu_backed` leg -- takes work of its own and runs only with --full.
 
 Rank 0 prints one JSON line.  `roofline` prices the launch against HBM with
 ALGORITHMIC bytes (M*N*2 in + 4P lags + 8 xy per localization; 6164 B at
@@ -60,6 +67,28 @@ def achievable_hbm():
 
 
 VALU_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector peak
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: write each array (torch or numpy, first axis = frames /
+    records) as dirname/<name>.npy, float32 as it is and every other dtype as
+    float64.  Outputs larger than DUMP_MAX_BYTES in all are cut to a fixed
+    seeded sample of rows, the same rows of every array, in ascending order."""
+    ts = {k: torch.as_tensor(v) for k, v in arrays.items()}
+    total = sum(t.numel() * (4 if t.dtype == torch.float32 else 8) for t in ts.values())
+    if total > DUMP_MAX_BYTES:
+        B = next(iter(ts.values())).shape[0]
+        assert all(t.shape[0] == B for t in ts.values())
+        n = B * (DUMP_MAX_BYTES - 256 * len(ts)) // total  # 256: room for each file's header
+        idx = np.sort(np.random.default_rng(0xD0).choice(B, n, replace=False))
+        ts = {k: t[torch.as_tensor(idx, device=t.device)] for k, t in ts.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, t in ts.items():
+        a = t.cpu().numpy()
+        np.save(os.path.join(dirname, k + ".npy"),
+                a if a.dtype in (np.float32, np.float64) else a.astype(np.float64))
+
 
 # BASELINE.json configs 1-5.  batch: per GPU (weak) or global (strong).
 CONFIGS = {
@@ -163,11 +192,17 @@ def parse():
     ap.add_argument("--streams", type=int, default=0,
                     help="configs 2-4: consecutive steps alternate over this many HIP streams, own outputs each "
                          "(0: 2 where a launch keeps no context scratch, else 1)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: parity, cpu_baseline, "
+                         "gpu_clock_mhz, config 5's latency_ms, config 1's gpu_backed leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: a fixed seeded sample of rows beyond that)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-rehearsal", action="store_true",
                     help="no GPU: rehearse the N-process launch, rank logic and JSON line over gloo "
                          "with a stand-in CPU step (tests/test_distributed.py); not a measurement")
-    ap.add_argument("--no-parity", action="store_true")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip parity")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend at N > 1 (nccl = RCCL; gloo: the N-rank code on one "
                          "GPU box, e.g. with --rank-device 0; never a measurement of N GPUs)")
@@ -186,6 +221,8 @@ def parse():
         a.warmup = {1: 10, 2: 20, 5: 20, 4: 2}.get(a.config, 3)
     if a.config in (1, 5):
         a.engine = "direct"  # the reference's integer path (per frame / streaming)
+    if not a.full:  # a plain run: only what the headline figure needs
+        a.no_cpu = a.no_parity = True
     return a
 
 
@@ -328,7 +365,11 @@ def time_engine(engine, args, dev, ri, cache):
                     args.warmup, sync=lambda: torch.cuda.synchronize(dev), device=dev,
                     on_start=start, on_end=lambda: (join(), ev1.record(stream)))
     kern_s = ev0.elapsed_time(ev1) / 1e3 / args.steps  # GPU time per launch, launch stream
-    clock = gpu_clock_mhz(dev, stream)
+    # the last timed step: launches[(steps - 1) % R], whose outputs are outs[that % Q]
+    out = outs[((args.steps - 1) % R) % Q]
+    if ri.rank == 0 and args.dump_outputs and engine == args.engine:  # not --also's second engine
+        dump_outputs(args.dump_outputs, out)
+    clock = gpu_clock_mhz(dev, stream) if args.full else None
     total = shard.sum_over_ranks([B * args.steps], device=dev)[0]
     # algorithmic bytes: frames in, lags + (x, y) out (+ xy_ls and its rms with LS)
     bytes_per_loc = M * N * 2 + 4 * P + 8 + (12 if ls else 0)
@@ -350,8 +391,9 @@ def time_engine(engine, args, dev, ri, cache):
         "ls": ls,
         "gpu_clock_mhz": clock,
     }
-    lags = out["lags"].cpu()
-    assert int(lags.abs().max()) <= loc.dims.S
+    if args.full:
+        lags = out["lags"].cpu()
+        assert int(lags.abs().max()) <= loc.dims.S
     if ri.rank == 0 and not args.no_parity:
         n = min(B, 65536)
         f0 = batches[0][:n].contiguous()
@@ -387,7 +429,15 @@ def time_stream(args, dev, ri, cache):
                     sync=lambda: (st.synchronize(), torch.cuda.synchronize(dev)), device=dev,
                     on_start=lambda: ev0.record(st), on_end=lambda: ev1.record(st))
     gpu_s = ev0.elapsed_time(ev1) / 1e3
-    clock = gpu_clock_mhz(dev, st)
+    if ri.rank == 0 and args.dump_outputs:
+        # the last timed hop's records (triggered slots sorted by stream) and the run's totals;
+        # ema_best / xy / max_L are defined for gated slots only (tdoa.h): zero elsewhere
+        rec = pipe.records()
+        for k in ("ema_best", "xy", "max_L"):
+            rec[k][rec["gate"] == 0] = 0
+        dump_outputs(args.dump_outputs, {**rec, "count": pipe.out["count"],
+                                         "totals": np.array(pipe.totals(), np.int64)})
+    clock = gpu_clock_mhz(dev, st) if args.full else None
     _, trig1, gated1 = pipe.totals()
     trig, gated = shard.sum_over_ranks([trig1 - trig0, gated1 - gated0], device=dev)
     # per-hop latency, outside the timed region: one hop in flight at a time,
@@ -397,7 +447,7 @@ def time_stream(args, dev, ri, cache):
     lat_host, lat_gpu = [], []
     e_a = torch.cuda.Event(enable_timing=True)
     e_b = torch.cuda.Event(enable_timing=True)
-    for _ in range(min(200, max(50, args.steps))):
+    for _ in range(min(200, max(50, args.steps)) if args.full else 0):
         t0 = time.perf_counter()
         e_a.record(st)
         pipe.step()
@@ -415,7 +465,7 @@ def time_stream(args, dev, ri, cache):
             "stream_samples_per_s": samples / t["wall_max_s"],
             "realtime_streams": samples / t["wall_max_s"] / cfg["fs"],
             "capture_bytes_per_step": ri.world * S * H * 3,
-            "latency_ms": {"p50": pct(lat_host, 50), "p99": pct(lat_host, 99),
+            "latency_ms": None if not args.full else {"p50": pct(lat_host, 50), "p99": pct(lat_host, 99),
                            "gpu_p50": pct(lat_gpu, 50), "gpu_p99": pct(lat_gpu, 99),
                            "hops": len(lat_host),
                            "kind": "per hop, one hop in flight: submit -> the hop's device outputs "
@@ -482,6 +532,12 @@ def time_config1(args, dev, ri, path):
     finally:
         L.tdoa_ref_set_device(int(dev.index))
     total = shard.sum_over_ranks([args.steps], device=dev)[0]
+    res = {"value": total / t["wall_max_s"], "ms_per_step": t["wall_max_s"] * 1e3 / args.steps,
+           "parity": None, "S": S, "win": win, "frames": fr,
+           "last": {"correlations": np.frombuffer(bytes(outs[n - 1].correlations), np.int64),
+                    "best_shift": np.array([outs[n - 1].best_shift], np.int64)}}
+    if not args.full:
+        return res
     # parity: the oracle's DC removal / normalise / window / xcorr / prior per frame
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import oracle as O
@@ -491,11 +547,10 @@ def time_config1(args, dev, ri, path):
         sc, best = O.xcorr(pre[0], pre[1], S)
         got = np.frombuffer(bytes(outs[i].correlations), np.int64)
         ok += int(outs[i].best_shift == best and (got == O.prior(sc, best)).all())
-    return {"value": total / t["wall_max_s"], "ms_per_step": t["wall_max_s"] * 1e3 / args.steps,
-            "parity": {"frames": args.steps, "bit_exact_frames": ok,
-                       "contract": "correlations (int64, after the lag prior) and best_shift equal "
-                                   "the oracle's for every timed frame"},
-            "S": S, "win": win, "frames": fr}
+    res["parity"] = {"frames": args.steps, "bit_exact_frames": ok,
+                     "contract": "correlations (int64, after the lag prior) and best_shift equal "
+                                 "the oracle's for every timed frame"}
+    return res
 
 
 def cpu_baseline_config1(args, res):
@@ -520,7 +575,9 @@ def cpu_baseline_config1(args, res):
 
 def main_config1(args, dev, ri):
     res = time_config1(args, dev, ri, "host")
-    gpu = time_config1(args, dev, ri, "gpu")
+    if ri.rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res["last"])  # the last timed frame's Correlations
+    gpu = time_config1(args, dev, ri, "gpu") if args.full else None
     world = shard.ranks_seen()
     if ri.rank == 0:
         cfg = CONFIGS[1]
@@ -538,7 +595,8 @@ def main_config1(args, dev, ri):
                        "parallelism": f"dp{world} (per-frame, no collective)"},
             "parity": res["parity"],
             "roofline": None,
-            "gpu_backed": {"value": gpu["value"], "ms_per_step": gpu["ms_per_step"], "parity": gpu["parity"],
+            "gpu_backed": None if gpu is None else {
+                           "value": gpu["value"], "ms_per_step": gpu["ms_per_step"], "parity": gpu["parity"],
                            "note": "the same seven calls with the GPU-backed symbols (default device): "
                                    "latency-bound, three GPU round trips per frame (each write_out's "
                                    "launch also computes the buffer's normalize and window); the batched "

@@ -41,6 +41,48 @@ def test_defaults_are_the_headline_run():
     assert a.preflight_s > 0 and _args("--preflight-s", "0").preflight_s == 0
 
 
+def test_plain_run_skips_what_full_adds():
+    a = _args()
+    assert not a.full and a.no_cpu and a.no_parity and a.dump_outputs is None
+    f = _args("--full")
+    assert f.full and not f.no_cpu and not f.no_parity
+    assert _args("--full", "--no-cpu").no_cpu and _args("--full", "--no-parity").no_parity
+    assert _args("--dump-outputs", "d").dump_outputs == "d"
+
+
+def test_dump_outputs_files(tmp_path):
+    import numpy as np
+    rng = np.random.default_rng(7)
+    arrays = {"lags": rng.integers(-46, 47, (1000, 3), dtype=np.int32),
+              "gate": rng.integers(0, 2, 1000, dtype=np.uint8),
+              "max_L": rng.integers(0, 1 << 40, 1000, dtype=np.int64),
+              "xy": rng.random((1000, 2), dtype=np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in arrays)
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == (np.float32 if v.dtype == np.float32 else np.float64)
+        assert got.shape == v.shape and (got == v).all()
+    # beyond the bound: the same seeded rows of every array, the same from call to call
+    real = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 10_000
+    try:
+        bench.dump_outputs(str(tmp_path / "a"), arrays)
+        bench.dump_outputs(str(tmp_path / "b"), arrays)
+    finally:
+        bench.DUMP_MAX_BYTES = real
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    n = a["gate"].shape[0]
+    assert 0 < n < 1000
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 10_000
+    # max_L's values are distinct: they identify the sampled rows
+    rows = [int(np.flatnonzero(arrays["max_L"] == int(v))[0]) for v in a["max_L"]]
+    assert rows == sorted(set(rows))
+    for k, v in arrays.items():
+        assert a[k].shape[0] == n and (a[k] == v[rows]).all()
+        assert (np.load(tmp_path / "b" / f"{k}.npy") == a[k]).all()
+
+
 def test_traffic_only_for_dispatched_kernels():
     tj = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
     t2, src = bench.traffic_entry(_args())

@@ -140,10 +140,10 @@ def test_bench_self_launches_two_ranks():
     """`python bench.py --gpus 2` (no torchrun around it) starts its two rank
     processes itself, before touching a GPU; here over gloo with the stand-in
     CPU step of --cpu-rehearsal.  One JSON line: both ranks joined, and the
-    rank-0 cpu_baseline is attached at N > 1 too."""
+    rank-0 cpu_baseline (--full) is attached at N > 1 too."""
     import json
     r = _bench("--gpus", "2", "--cpu-rehearsal", "--steps", "3", "--warmup", "1",
-               "--cpu-seconds", "0.5")
+               "--full", "--cpu-seconds", "0.5")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

@@ -23,7 +23,7 @@ def test_bench_two_ranks_on_one_gpu(config):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
             "--rank-device", "0", "--config", str(config), "--steps", "5", "--warmup", "2",
-            "--cpu-seconds", "0.5", "--no-parity"]
+            "--full", "--cpu-seconds", "0.5", "--no-parity"]
     if config == 2:
         argv += ["--rotate-mib", "16", "--preflight-s", "0"]
     else:

@@ -88,7 +88,7 @@ for step in "$@"; do
         ;;
     bench)
         c=$(field "$step" 2 2); e=$(field "$step" 3 gcc_phat)
-        timeout -k 10 400 python bench.py --config $c --engine $e $BENCH_ARGS > "$OUT/bench_c${c}_$e.log" 2>&1 \
+        timeout -k 10 400 python bench.py --full --config $c --engine $e $BENCH_ARGS > "$OUT/bench_c${c}_$e.log" 2>&1 \
             || { echo "bench failed"; tail -5 "$OUT/bench_c${c}_$e.log"; exit 22; }
         tail -1 "$OUT/bench_c${c}_$e.log" > "$OUT/bench_c${c}_$e.json"
         cut -c1-400 "$OUT/bench_c${c}_$e.json"

@@ -32,7 +32,7 @@ namespace {
 // z[n] = x[2n] + i x[2n+1] (z = 0 for n >= N/2) plus a split step; every
 // pair's real inverse FFT_L is one complex inverse FFT_N' of
 // Y[k] = (R[k] + R*[N'-k]) + i (R[k] - R*[N'-k]) e^{+2 pi i k / L},
-// R = conj(X_i) X_j / max(|X_i^* X_j|, eps)   (PHAT),
+// U_m = X_m / sqrt(|X_m|^2 + eps),  R = conj(U_i) U_j   (PHAT, per-mic floor),
 // y = IFFT(Y)/L  ->  r[2n] = Re y[n], r[2n+1] = Im y[n].
 // FFTs: Stockham autosort radix-4 (+ one radix-2 pass when log2 N' is odd)
 // in LDS, all M (then P) transforms of the frame advanced together.
@@ -147,7 +147,7 @@ __device__ void fft_rest(cf *buf, int stride, int n, int Ns0, const float *tw)
 template <int M>
 __global__ void __launch_bounds__(512) k_gcc_phat(tdoa_kparams kp, tdoa_kout out,
                                                   const int16_t *__restrict__ frames, int64_t B,
-                                                  float eps2)
+                                                  float eps)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int P = M * (M - 1) / 2;
@@ -219,6 +219,11 @@ __global__ void __launch_bounds__(512) k_gcc_phat(tdoa_kparams kp, tdoa_kout out
                 const cf od2 = cmul(w2n, d2);
                 Xn[m] = {0.5f * (e2.x + od2.y), 0.5f * (e2.y - od2.x)};
             }
+            // U = X / sqrt(|X|^2 + eps): x is scaled by 2^-15 here, eps as given
+            const float rk = rsqrtf(Xk[m].x * Xk[m].x + Xk[m].y * Xk[m].y + eps);
+            const float rn = rsqrtf(Xn[m].x * Xn[m].x + Xn[m].y * Xn[m].y + eps);
+            Xk[m] = {Xk[m].x * rk, Xk[m].y * rk};
+            Xn[m] = {Xn[m].x * rn, Xn[m].y * rn};
         }
 #pragma unroll
         for (int p = 0; p < P; p++) {
@@ -234,10 +239,6 @@ __global__ void __launch_bounds__(512) k_gcc_phat(tdoa_kparams kp, tdoa_kout out
             }
             cf Rk = cmul(cconj(Xk[i]), Xk[jj]);
             cf Rn = cmul(cconj(Xn[i]), Xn[jj]);
-            const float ak = Rk.x * Rk.x + Rk.y * Rk.y, an = Rn.x * Rn.x + Rn.y * Rn.y;
-            const float rk = rsqrtf(fmaxf(ak, eps2)), rn = rsqrtf(fmaxf(an, eps2));
-            Rk = {Rk.x * rk, Rk.y * rk};
-            Rn = {Rn.x * rn, Rn.y * rn};
             // Y[k] = (R[k] + R*[n-k]) + i (R[k] - R*[n-k]) conj(w^k)
             const cf ae = cadd(Rk, cconj(Rn));
             const cf ao = cmul(csub(Rk, cconj(Rn)), cconj(w2k));
@@ -397,7 +398,7 @@ __device__ __forceinline__ void grid_tail(const tdoa_kparams &kp, const tdoa_kou
 
 __global__ void __launch_bounds__(192, 1) k_gcc_phat_1024(tdoa_kparams kp, tdoa_kout out,
                                                           const int16_t *__restrict__ frames,
-                                                          int64_t B, float eps2)
+                                                          int64_t B, float e2)
 {
     constexpr int M = 3, P = 3, N = 1024;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -473,7 +474,7 @@ __global__ void __launch_bounds__(192, 1) k_gcc_phat_1024(tdoa_kparams kp, tdoa_
         //      Only the low byte of x - off survives `<<= 8`, so with s = sext8(x - off)
         //      the windowed sample is ((s << 8) * W) >> 15 = floor(s * W / 128), an
         //      integer below 2^23: exact in fp32 (wf holds W / 128).  Samples stay in
-        //      int16 units (PHAT is scale-invariant; eps2 is scaled to match).
+        //      int16 units (PHAT is scale-invariant; the floor e2 is scaled to match).
         int s = 0;
 #pragma unroll
         for (int t = 0; t < 16; t++)
@@ -555,8 +556,11 @@ __global__ void __launch_bounds__(192, 1) k_gcc_phat_1024(tdoa_kparams kp, tdoa_
                     const f2 a = Zk[q][m], b = Zn[q][m];
                     const f2 e = a + conjf2(b), d = cmulf(w2k, a - conjf2(b));
                     Xk[m] = 0.5f * f2{e.x + d.y, e.y - d.x};
-                    const f2 e2 = b + conjf2(a), d2 = cmulf(w2n, b - conjf2(a));
-                    Xn[m] = 0.5f * f2{e2.x + d2.y, e2.y - d2.x};
+                    const f2 en = b + conjf2(a), dn = cmulf(w2n, b - conjf2(a));
+                    Xn[m] = 0.5f * f2{en.x + dn.y, en.y - dn.x};
+                    // U = X / sqrt(|X|^2 + e2), the per-mic floor in this kernel's units
+                    Xk[m] *= __builtin_amdgcn_rsqf(Xk[m].x * Xk[m].x + Xk[m].y * Xk[m].y + e2);
+                    Xn[m] *= __builtin_amdgcn_rsqf(Xn[m].x * Xn[m].x + Xn[m].y * Xn[m].y + e2);
                 }
                 if (live[q]) {
 #pragma unroll
@@ -564,8 +568,6 @@ __global__ void __launch_bounds__(192, 1) k_gcc_phat_1024(tdoa_kparams kp, tdoa_
                         const int i = p < 2 ? 0 : 1, j = p == 0 ? 1 : 2;
                         f2 Rk = cmulf(conjf2(Xk[i]), Xk[j]);
                         f2 Rn = cmulf(conjf2(Xn[i]), Xn[j]);
-                        Rk *= __builtin_amdgcn_rsqf(fmaxf(Rk.x * Rk.x + Rk.y * Rk.y, eps2));
-                        Rn *= __builtin_amdgcn_rsqf(fmaxf(Rn.x * Rn.x + Rn.y * Rn.y, eps2));
                         bufs[fo[q] + p * 1024 + ik[q]] =
                             (Rk + conjf2(Rn)) + times_i(cmulf(Rk - conjf2(Rn), conjf2(w2k)));
                         bufs[fo[q] + p * 1024 + ikn[q]] =
@@ -775,10 +777,12 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
                          int64_t B, float phat_eps, void *spec_scratch, size_t spec_bytes,
                          void *stream)
 {
-    // |X_i^* X_j|^2 floor; kept a normal float (v_rsq_f32 flushes denormals)
-    float eps2 = phat_eps * phat_eps;
-    if (!(eps2 >= 1e-30f))
-        eps2 = 1e-30f;
+    // the per-mic floor of U_m = X_m / sqrt(|X_m|^2 + eps) (include/tdoa.h), x
+    // scaled by 2^-15; kept a normal float (v_rsq_f32 flushes denormals, and a
+    // zero bin must stay 0).  Each kernel gets it in the units of its own spectra.
+    float eps = phat_eps;
+    if (!(eps >= 1e-30f))
+        eps = 1e-30f;
     if (((uintptr_t)frames & 15) != 0)
         return tdoa_set_error(-1, "frames must be 16-byte aligned");
     if (!kp.tw || !kp.tw2)
@@ -794,7 +798,7 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return tdoa_launch_phat_r16(kp, out, frames, B, phat_eps, spec_scratch, spec_bytes, stream);
     if (route == PhatRoute::SPLIT)
         return tdoa_launch_gcc_phat_split(kp, out, frames, B,
-                                          eps2 * 1152921504606846976.0f /* 2^60: int16 units */,
+                                          eps * 1073741824.0f /* 2^30: int16 units */,
                                           spec_scratch, spec_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     if (route == PhatRoute::FUSED_1024) {
@@ -807,7 +811,7 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
         const int64_t iters = (npairs + resident - 1) / resident;
         const int64_t grid = (npairs + iters - 1) / iters;
         hipLaunchKernelGGL(k_gcc_phat_1024, dim3((unsigned)grid), dim3(192), lds1024, st, kp, out,
-                           frames, B, eps2 * 1152921504606846976.0f /* 2^60: int16 units */);
+                           frames, B, eps * 1073741824.0f /* 2^30: int16 units */);
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? 0 : hip_fail(e, "k_gcc_phat_1024 launch");
     }
@@ -823,9 +827,9 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
     if (B > INT_MAX)
         return tdoa_set_error(-1, "GCC_PHAT: batch too large for one launch");
     if (kp.M == 2)
-        hipLaunchKernelGGL(k_gcc_phat<2>, dim3((unsigned)B), dim3(threads), lds, st, kp, out, frames, B, eps2);
+        hipLaunchKernelGGL(k_gcc_phat<2>, dim3((unsigned)B), dim3(threads), lds, st, kp, out, frames, B, eps);
     else if (kp.M == 3)
-        hipLaunchKernelGGL(k_gcc_phat<3>, dim3((unsigned)B), dim3(threads), lds, st, kp, out, frames, B, eps2);
+        hipLaunchKernelGGL(k_gcc_phat<3>, dim3((unsigned)B), dim3(threads), lds, st, kp, out, frames, B, eps);
     else
         return tdoa_set_error(-1, "GCC_PHAT: num_mics must be 2 or 3 for now");
     hipError_t e = hipGetLastError();

@@ -261,5 +261,5 @@ bool tdoa_grid_bb_compact(const tdoa_kparams &kp);
 bool tdoa_gcc_phat_grid_in_kernel(const tdoa_kparams &kp);
 bool tdoa_gcc_phat_peak3(const tdoa_kparams &kp);
 int tdoa_launch_gcc_phat_split(const tdoa_kparams &kp, const tdoa_kout &out,
-                               const int16_t *frames, int64_t B, float eps2_int16,
+                               const int16_t *frames, int64_t B, float eps_int16,
                                void *scratch, size_t scratch_bytes, void *stream);

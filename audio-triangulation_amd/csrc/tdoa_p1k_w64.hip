@@ -23,7 +23,7 @@
 //   with partner residues (r, 64 - r), so the real-FFT split (bins b, N - b)
 //   is in-lane after a DPP swap of the upper eight registers (lane 0: residue
 //   0, a one-register rotation; lane 1: residue 32, self-paired).
-//   PHAT per mic: U = X / max(|X|, sqrt(e)) (as k_p1k_lean).
+//   PHAT per mic: U = X / sqrt(|X|^2 + e) (as k_p1k_lean).
 // Per pair (0,1), (0,2), (1,2) (sample_compute.h:120-122 order):
 //   Y[b] = (R[b] + R*[N-b]) + i (R[b] - R*[N-b]) W_2048^{-b}, R = conj(U_i) U_j,
 //   y = IFFT_1024(Y) pruned to n in [0, 32) u [992, 1024) (lags -64..63):
@@ -377,7 +377,10 @@ __device__ __forceinline__ f2 w64_spectrum(const W64Lane &W, const uint32_t (&w)
     w64_front(W, w, V);
     after_front();
     w64_fft_fwd(W, V);
-    const f2 x512 = c_unit(conjf2(V[8]), e2);  // bin 512 (lane 0, residue 0)
+    // bin 512 (lane 0, residue 0) is X where the split's bins hold 2 X: floor e2 / 4 (as k_p1k_lean)
+    float e2q;
+    asm volatile("v_ldexp_f32 %0, %1, -2" : "=v"(e2q) : "s"(e2));
+    const f2 x512 = c_unit(conjf2(V[8]), e2q);
     w64_swap_upper<true>(V, f2{0.0f, 0.0f});
     return x512;
 }

@@ -21,10 +21,9 @@
 //       residue 0, self-paired with two fixed points 0 and 512 -- rotates its
 //       upper half instead and keeps bin 512 in a 33rd register; lane 1 --
 //       residue 16, self-paired -- keeps its registers).
-//   PHAT factored per mic: U_m = X_m / max(|X_m|, sqrt(e)), so
-//       R_ij = conj(U_i) U_j is the unit cross-spectrum.  Equal to the oracle's
-//       R / max(|R|, eps) whenever |X_i|, |X_j| >= sqrt(eps) (every nonzero bin
-//       of an integer frame in practice; an all-zero bin gives 0 either way).
+//   PHAT factored per mic: U_m = X_m / sqrt(|X_m|^2 + e) (c_unit), so
+//       R_ij = conj(U_i) U_j is the unit cross-spectrum: the definition of
+//       include/tdoa.h and the oracle (an all-zero bin gives 0).
 // Per pair (0,1), (0,2), (1,2) (sample_compute.h:120-122 order):
 //   Y[b] = (R[b] + R*[N-b]) + i (R[b] - R*[N-b]) W_2048^{-b}   (in-lane pairs)
 //   swap back to residue columns, y = IFFT_1024(Y) pruned to the outputs
@@ -223,11 +222,6 @@ __device__ __forceinline__ void sts_f2(char *base, int off, f2 v)
 // passes from sinking a finished partial sum past later phases)
 __device__ __forceinline__ void pin(f2 &x) { asm volatile("" : "+v"(x)); }
 
-__device__ __forceinline__ f2 unit(f2 x, float e2)
-{
-    return x * __builtin_amdgcn_rsqf(fmaxf(x.x * x.x + x.y * x.y, e2));
-}
-
 
 struct Lane {
     int hw;           // half-wave of the wave
@@ -333,8 +327,16 @@ __device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)
     }
     after_front();  // the row's words are consumed
     fft_col_lds<false, true>(L, v, L.tileA);
+    // X[512] = conj(Z[512]) is in units of X where every other bin holds 2 X
+    // (the split's e, od), so its floor is e2 / 4.  One v_ldexp per row, issued
+    // here under the transpose's LDS round trip (volatile: computed once per
+    // kernel instead, the value costs a register the kernel does not have and
+    // spills; config 2 measured 26.96 us per step here, 27.24 next to its use,
+    // 27.01 without it)
+    float e2q;
+    asm volatile("v_ldexp_f32 %0, %1, -2" : "=v"(e2q) : "s"(e2));
     fft_row_fwd(L, L.tileA, V);
-    V[32] = c_unit(conjf2(V[16]), e2);
+    V[32] = c_unit(conjf2(V[16]), e2q);
     swap_upper_exec<true>(V, f2{0.0f, 0.0f});
 }
 
@@ -1283,8 +1285,8 @@ bool tdoa_phat1024_fits(const tdoa_kparams &kp)
 int tdoa_launch_phat1024(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames,
                          int64_t B, float phat_eps, void *stream)
 {
-    // per-mic clamp: |X_m| >= sqrt(eps) in the oracle's units (x / 2^15, X / 2),
-    // i.e. |X|^2 >= eps * 2^32 in the kernel's int16 units with the split's factor 2
+    // per-mic floor: |X_m|^2 + eps in the oracle's units (x / 2^15, X / 2),
+    // i.e. |X|^2 + eps * 2^32 in the kernel's int16 units with the split's factor 2
     float e2 = phat_eps * 4294967296.0f;
     if (!(e2 >= 1e-30f))
         e2 = 1e-30f;

@@ -9,7 +9,7 @@
 //                FFT as three register passes (radix C/256, 16, 16; Stockham
 //                order through one padded LDS buffer), the real-FFT split to
 //                X[0..C] of the 2C-point real transform, and the per-mic PHAT
-//                factor U = X / max(|X|, sqrt(eps)), stored as C + 1 bins.
+//                factor U = X / sqrt(|X|^2 + eps), stored as C + 1 bins.
 //   k_pair16<C>  one workgroup per (frame, pair): R = conj(U_i) U_j is already
 //                the unit cross spectrum; the inverse pre-twiddle packs it
 //                into C bins whose inverse C-point FFT holds the correlation
@@ -23,8 +23,8 @@
 // and the same bins of Y before the inverse, so neither end needs a transpose;
 // the partner bin C - b of the split and of the pre-twiddle is read from LDS /
 // the scratch.  LDS index i is padded to i + i/16 (conflict-free b64 access for
-// every pass's stride).  Same definition as oracle/gcc_phat_oracle.py; the PHAT
-// factorisation equals its R / max(|R|, eps) whenever |X_i|, |X_j| >= sqrt(eps).
+// every pass's stride).  Same definition as oracle/gcc_phat_oracle.py, the
+// per-mic PHAT floor included.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -2630,8 +2630,8 @@ int tdoa_launch_phat_r16(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return tdoa_set_error(-1, "GCC_PHAT r16: unsupported shape");
     if (!scratch)
         return tdoa_set_error(-1, "GCC_PHAT: context has no spectrum scratch");
-    // per-mic clamp |X_m| >= sqrt(eps) in the oracle's units (x / 2^15, X / 2):
-    // |X|^2 >= eps * 2^32 in the kernel's int16 units with the split's factor 2
+    // per-mic floor |X_m|^2 + eps in the oracle's units (x / 2^15, X / 2):
+    // |X|^2 + eps * 2^32 in the kernel's int16 units with the split's factor 2
     float e2 = phat_eps * 4294967296.0f;
     if (!(e2 >= 1e-30f))
         e2 = 1e-30f;
@@ -2643,12 +2643,13 @@ int tdoa_launch_phat_r16(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return launch_frame16<4096, 4>(kp, out, frames, B, e2, st);
     if (kp.N == 4096 && kp.M == 3)
         return launch_frame16<4096, 3>(kp, out, frames, B, e2, st);
-    if (kp.N == 2048 && kp.M == 8)
+    if (kp.N == 2048 && kp.M == 8) {
 #if TDOA_AB
         if (frame16w_pick())
             return launch_frame16w<2048, 8>(kp, out, frames, B, e2, st);
 #endif
         return launch_frame16<2048, 8>(kp, out, frames, B, e2, st);
+    }
     if (kp.N == 2048 && kp.M == 4)
         return launch_frame16<2048, 4>(kp, out, frames, B, e2, st);
     return kp.N == 4096 ? launch_r16<4096>(kp, out, frames, B, e2, scratch, scratch_bytes, st)

@@ -15,7 +15,8 @@
 //                   (correlations.c:20-33 semantics on float scores);
 //   k_phat_gate     sum of squared best lags > 4 (sample_compute.h:124-134).
 //
-// Samples stay in int16 units; the launcher scales eps^2 by 2^60 to match.
+// Samples stay in int16 units; the launcher scales the per-mic floor eps by
+// 2^30 to match (|X|^2 here is 2^30 times that of x / 2^15).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -203,7 +204,7 @@ __device__ __forceinline__ void load_bins(const f2 *X, int k, int kn, f2 &xk, f2
 
 __global__ void __launch_bounds__(TPB) k_phat_pairs(tdoa_kparams kp, tdoa_kout out,
                                                     const f2 *__restrict__ spec, int64_t f_begin,
-                                                    int64_t nblocks, float eps2)
+                                                    int64_t nblocks, float e2)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f2 *buf = (f2 *)smem;                    // [N]
@@ -220,15 +221,17 @@ __global__ void __launch_bounds__(TPB) k_phat_pairs(tdoa_kparams kp, tdoa_kout o
     const f2 *Xi = spec + (size_t)(fl * M + kp.pair_i[p]) * N;
     const f2 *Xj = spec + (size_t)(fl * M + kp.pair_j[p]) * N;
 
-    // R = conj(X_i) X_j / max(|.|, eps);  Y[k] = (R[k] + R*[N-k]) + i (R[k] - R*[N-k]) conj(W_2N^k)
+    // U = X / sqrt(|X|^2 + e2), R = conj(U_i) U_j;  Y[k] = (R[k] + R*[N-k]) + i (R[k] - R*[N-k]) conj(W_2N^k)
     for (int k = tid; k <= N / 2; k += TPB) {
         const int kn = (N - k) & (N - 1);
         f2 ik, in, jk, jn;
         load_bins(Xi, k, kn, ik, in);
         load_bins(Xj, k, kn, jk, jn);
-        f2 Rk = cmul(conj2(ik), jk), Rn = cmul(conj2(in), jn);
-        Rk *= __builtin_amdgcn_rsqf(fmaxf(Rk.x * Rk.x + Rk.y * Rk.y, eps2));
-        Rn *= __builtin_amdgcn_rsqf(fmaxf(Rn.x * Rn.x + Rn.y * Rn.y, eps2));
+        ik *= __builtin_amdgcn_rsqf(ik.x * ik.x + ik.y * ik.y + e2);
+        in *= __builtin_amdgcn_rsqf(in.x * in.x + in.y * in.y + e2);
+        jk *= __builtin_amdgcn_rsqf(jk.x * jk.x + jk.y * jk.y + e2);
+        jn *= __builtin_amdgcn_rsqf(jn.x * jn.x + jn.y * jn.y + e2);
+        const f2 Rk = cmul(conj2(ik), jk), Rn = cmul(conj2(in), jn);
         const f2 w2k = ldtw(kp.tw2, k), w2n = ldtw(kp.tw2, N - k);
         buf[k] = (Rk + conj2(Rn)) + mul_i(cmul(Rk - conj2(Rn), conj2(w2k)));
         if (k != 0 && k != N / 2)
@@ -313,7 +316,7 @@ int fail_hip(hipError_t e, const char *what)
 int64_t tdoa_phat_split_row_bytes(int N) { return (int64_t)N * 8; }
 
 int tdoa_launch_gcc_phat_split(const tdoa_kparams &kp, const tdoa_kout &out,
-                               const int16_t *frames, int64_t B, float eps2_int16,
+                               const int16_t *frames, int64_t B, float eps_int16,
                                void *scratch, size_t scratch_bytes, void *stream)
 {
     const int N = kp.N, M = kp.M, P = kp.P;
@@ -337,7 +340,7 @@ int tdoa_launch_gcc_phat_split(const tdoa_kparams &kp, const tdoa_kout &out,
         hipLaunchKernelGGL(k_phat_spectra, dim3((unsigned)(nf * M)), dim3(TPB), lds1, st, kp, frames,
                            c0 * M, (f2 *)scratch);
         hipLaunchKernelGGL(k_phat_pairs, dim3((unsigned)(nf * P)), dim3(TPB), lds2, st, kp, out,
-                           (const f2 *)scratch, c0, nf * P, eps2_int16);
+                           (const f2 *)scratch, c0, nf * P, eps_int16);
     }
     if (out.gate) {
         const int64_t g = (B + 255) / 256;

@@ -80,7 +80,10 @@ typedef struct tdoa_config {
      * buffer.c:8 is undefined) DPSS(N, NW=2) normalised to max 1, x32767,
      * rounded (window.ipynb procedure).  Copied. */
     const int32_t *window_q15;
-    float phat_eps;          /* GCC_PHAT: floor of |X_i^* X_j| (samples scaled by 2^-15), default 1e-12 */
+    /* GCC_PHAT: per-mic soft floor, U_m = X_m / sqrt(|X_m|^2 + phat_eps),
+     * R_ij = conj(U_i) U_j, with samples scaled by 2^-15 and X the 2N-point
+     * spectrum; default 1e-12. */
+    float phat_eps;
 } tdoa_config;
 
 /* Per-frame results (device pointers; any may be NULL unless noted). */

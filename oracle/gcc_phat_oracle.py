@@ -7,7 +7,8 @@ oracle defines it:
   x      = prep(frame) / 2^15       prep = rolling_buffer.c:64-66 DC removal,
                                     buffer.c:13-16 <<8 wrap, buffer.c:4-11 window
   X_m    = rfft(x_m, L = 2N)        zero-padded: linear (not circular) lags
-  R_ij   = conj(X_i) X_j / max(|conj(X_i) X_j|, eps)      (PHAT)
+  U_m    = X_m / sqrt(|X_m|^2 + eps)   (PHAT with a per-mic soft floor: the
+  R_ij   = conj(U_i) U_j                 definition of include/tdoa.h phat_eps)
   r_ij   = irfft(R_ij, L)           r[s] peaks at s = d when mic j lags mic i by d,
                                     the sign of correlations.c:9-16
   scores = r[s mod L], s = -S..S;   best = first max (correlations.c:20-23)
@@ -47,14 +48,14 @@ def gcc_phat_batch(frames, S, window, lut=None, eps=1e-12, half_w=50, half_h=50,
     B, M, N = x.shape
     L = 2 * N
     X = np.fft.rfft(x, L, axis=-1)
+    U = X / np.sqrt(X.real ** 2 + X.imag ** 2 + eps)
     pairs = [(i, j) for i in range(M) for j in range(i + 1, M)]
     P, K = len(pairs), 2 * S + 1
     s_idx = np.arange(-S, S + 1) % L
     scores = np.zeros((B, P, K))
     for p, (i, j) in enumerate(pairs):
-        R = np.conj(X[:, i]) * X[:, j]
-        R = R / np.maximum(np.abs(R), eps)
-        r = np.fft.irfft(R, L, axis=-1)
+        R = np.conj(U[:, i]) * U[:, j]
+        r =np.fft.irfft(R, L, axis=-1)
         scores[:, p] = r[:, s_idx]
     best = np.argmax(scores, axis=-1)  # first max
     lags = (best - S).astype(np.int32)

@@ -17,6 +17,10 @@ layout.  So, per shape and input kind, this asserts:
 Inputs: ADC-like integer-delay frames (the bench's generator), noise-only
 frames (flat scores, weak grid bounds) and a ragged batch (a partly filled last
 workgroup / wave).  Reference: correlations.c:20-33, vga_heatmap.h:99-108.
+  4. configs 3/4 with TDOA_F16_CHUNK=512 (the compact scratch of one chunk of
+     frames at a time, reused; read once per process, so a child process): whole
+     chunks (B = 2048) and a last chunk of 5 frames (B = 2053) bit-equal to the
+     unchunked run, the least squares over the full batch included.
 """
 import os
 import subprocess
@@ -125,5 +129,32 @@ def test_bench_path_equals_checked_path(shape, tmp_path):
     assert "child ok " + kernel in r.stdout
     child = np.load(tmp_path / "child.npz")
     for kind in KINDS:
+        for k, v in mine[kind].items():
+            assert np.array_equal(child[f"{kind}.{k}"], v), (shape, kind, k)
+
+
+@pytest.mark.parametrize("shape", ["cfg3", "cfg4"])
+def test_chunked_compact_path_equals_unchunked(shape, tmp_path):
+    ls = SHAPES[shape][5]
+    kinds = ("adc", "ragged")
+    loc = _localizer(shape)
+    mine = {}
+    for kind in kinds:
+        fr = _frames(shape, kind, loc)
+        assert fr.shape[0] > 4 * 512 - 1
+        np.save(tmp_path / f"{kind}.npy", fr.cpu().numpy())
+        mine[kind] = _bench_outputs(loc, fr, ls)
+        assert set(mine[kind]) == set(OUT_KEYS) - (set() if ls else {"xy_ls", "ls_rms"})
+    kernel = loc.batch_kernel()
+    loc.close()
+    code = CHILD.format(pkg=os.path.join(ROOT, "audio-triangulation_amd"), tests=os.path.join(ROOT, "tests"),
+                        shape=shape, kinds=kinds, tmp=str(tmp_path))
+    env = dict(os.environ, TDOA_F16_CHUNK="512")
+    env.pop("TDOA_NO_COMPACT", None)
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert "child ok " + kernel in r.stdout
+    child = np.load(tmp_path / "child.npz")
+    for kind in kinds:
         for k, v in mine[kind].items():
             assert np.array_equal(child[f"{kind}.{k}"], v), (shape, kind, k)

@@ -19,6 +19,10 @@ The defaults (k_frame16, deferred lagged epilogue at configs 3 and 4) run in
 test_gpu_gcc_phat.py itself.  k_frame16w and the fused grid are A/B paths that
 measured slower: they are built only into tdoa/libtdoa_ab.so (Makefile "ab",
 TDOA_AB=1), which those children load through TDOA_LIB; libtdoa.so has neither.
+
+The A/B library's own dispatch of the shapes that are not config 4's runs with no
+variant set: (4, 2048) must take k_frame16<2048, 4> and a two-pass shape
+(5, 2048) k_spec16, as in libtdoa.so.
 """
 import os
 import subprocess
@@ -40,7 +44,7 @@ from tdoa import synth
 from tdoa.localizer import Localizer
 from test_gpu_gcc_phat import check_phat, _np, _grid_f32
 M, N = {M}, {N}
-xy = synth.square_mics(0.15) if M == 4 else synth.circle_mics(8, 0.15)
+xy = synth.square_mics(0.15) if M == 4 else synth.circle_mics(M, 0.15)
 kw = dict(num_mics=M, frame_len=N, sample_rate_hz=50000, mic_xy=xy)
 ph = Localizer(engine="gcc_phat", **kw)
 S = ph.dims.S
@@ -82,3 +86,15 @@ def test_frame16_variant_vs_fp64(env, M, N):
         assert "variant ok k_frame16w" in r.stdout, r.stdout
     if env.get("TDOA_F16_FG") == "1":
         assert "grid_fused True" in r.stdout, r.stdout
+
+
+@pytest.mark.parametrize("M,N,kernel", [(4, 2048, "k_frame16"), (5, 2048, "k_spec16")])
+def test_ab_library_dispatch_vs_fp64(M, N, kernel):
+    code = CHILD.format(pkg=os.path.join(ROOT, "audio-triangulation_amd"), orc=os.path.join(ROOT, "oracle"),
+                        tests=os.path.join(ROOT, "tests"), M=M, N=N)
+    e = dict(os.environ, TDOA_LIB=AB_LIB)
+    for k in ("TDOA_F16", "TDOA_F16_DEFER", "TDOA_F16_FG"):
+        e.pop(k, None)
+    r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert f"variant ok {kernel} " in r.stdout, r.stdout

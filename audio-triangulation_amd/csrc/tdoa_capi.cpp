@@ -221,6 +221,8 @@ struct tdoa_ctx {
     size_t cscratch_bytes = 0;
     void *d_tscratch = nullptr;  // [B][P][3] float peak scores (least squares)
     size_t tscratch_bytes = 0;
+    void *d_pscratch = nullptr;  // tdoa_peaks: [B][Kp][P] lag tuples when only the refinement reads them
+    size_t pscratch_bytes = 0;
     std::vector<uint8_t> bb_img;  // k_grid_bb tables: tiles | ranges | tuples | uidx | queries
     std::vector<uint16_t> bb_rng; // [NT][P] lo | hi << 8 (host copy)
     void *d_fgq = nullptr;        // kp.fg_q
@@ -432,6 +434,9 @@ void free_device(tdoa_ctx *c)
     (void)hipFree(c->d_rscratch);
     (void)hipFree(c->d_cscratch);
     (void)hipFree(c->d_tscratch);
+    (void)hipFree(c->d_pscratch);
+    c->d_pscratch = nullptr;
+    c->pscratch_bytes = 0;
     (void)hipFree(c->d_mic);
     (void)hipFree(c->d_lut);
     c->d_lut = nullptr;
@@ -1063,6 +1068,52 @@ extern "C" int tdoa_heatmap(tdoa_ctx *ctx, const void *weighted, const void *max
         return fail(TDOA_ERR_INVALID, "tdoa_heatmap: negative batch");
     HIP_TRY(hipSetDevice(ctx->device));
     return tdoa_launch_heatmap(ctx->kp, weighted, max_L, is_float != 0, B, classes, stream);
+}
+
+extern "C" int tdoa_peaks(tdoa_ctx *ctx, const void *scores, int is_float, int64_t B,
+                          const tdoa_peaks_params *prm, const tdoa_peaks_outputs *out, void *stream)
+{
+    if (!ctx || !scores || !prm || !out)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: NULL argument");
+    if (!out->cell)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: outputs.cell is required");
+    if (B < 0)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: negative batch");
+    if (B > INT32_MAX)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: batch too large for one launch");
+    if (prm->num_peaks < 1 || prm->num_peaks > TDOA_MAX_PEAKS)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: num_peaks %d outside 1..%d", (int)prm->num_peaks,
+                    TDOA_MAX_PEAKS);
+    if (prm->radius < 0)
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: negative radius");
+    if (!tdoa_peaks_fits(ctx->kp, is_float != 0))
+        return fail(TDOA_ERR_INVALID, "tdoa_peaks: the L map and one frame's scores (%zu bytes) exceed the LDS budget",
+                    tdoa_peaks_lds(ctx->kp, is_float != 0));
+    if (B == 0)
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int Kp = prm->num_peaks;
+    const bool ls = out->xy_ls || out->ls_rms;
+    tdoa_peaks_kout k;
+    k.count = out->count;
+    k.cell = out->cell;
+    k.xy = out->xy;
+    k.L = out->L;
+    k.Lf = out->Lf;
+    k.lags = out->lags;
+    if (ls && !k.lags) {  // the refinement reads each peak's lag tuple
+        int rc = grow(&ctx->d_pscratch, &ctx->pscratch_bytes, (size_t)B * Kp * ctx->P * sizeof(int32_t), stream,
+                      "peak-lag");
+        if (rc)
+            return rc;
+        k.lags = (int32_t *)ctx->d_pscratch;
+    }
+    int rc = tdoa_launch_peaks(ctx->kp, k, scores, is_float != 0, B, Kp, prm->radius, prm->min_rel, stream);
+    if (rc != 0 || !ls)
+        return rc;
+    // B * Kp virtual frames: row f refines peak f % Kp of frame f / Kp
+    return tdoa_launch_ls(ctx->kp, scores, is_float != 0, nullptr, k.lags, k.cell, out->xy_ls, out->ls_rms,
+                          B * Kp, stream, Kp);
 }
 
 // accessors for the streaming pipeline (tdoa_stream.cpp)

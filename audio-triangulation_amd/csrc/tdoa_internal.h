@@ -165,6 +165,17 @@ struct tdoa_kout {
     float *weighted_c;
 };
 
+// Outputs of k_peaks (tdoa_peaks.hip): tdoa_peaks_outputs without the
+// refinement's fields; cell is never null (scratch if the caller passed none).
+struct tdoa_peaks_kout {
+    int32_t *count;
+    int32_t *cell;
+    float *xy;
+    int64_t *L;
+    float *Lf;
+    int32_t *lags;
+};
+
 // Streaming state of one pipeline (tdoa_stream.hip); all device pointers.
 struct tdoa_stream_params {
     int32_t M, N, H, log2N, fs;
@@ -223,9 +234,19 @@ bool tdoa_direct_fused_grid(const tdoa_kparams &kp);
 bool tdoa_direct_ema_fits(const tdoa_kparams &kp);
 int tdoa_launch_heatmap(const tdoa_kparams &kp, const void *weighted, const void *max_L,
                         bool is_float, int64_t B, uint8_t *classes, void *stream);
+// per_frame > 0 (tdoa_peaks): the B rows are per_frame peaks of each of
+// B / per_frame score frames -- row f reads the scores of frame f / per_frame,
+// and a row whose cell is negative (an empty slot) gets NaN instead of the clamp
 int tdoa_launch_ls(const tdoa_kparams &kp, const void *scores, bool is_float, const float *peak3,
                    const int32_t *lags, const int32_t *cells, float *xy_ls, float *rms,
-                   int64_t B, void *stream);
+                   int64_t B, void *stream, int per_frame = 0);
+// k_peaks (tdoa_peaks.hip): its dynamic LDS for this context and score type,
+// and whether that fits the budget
+size_t tdoa_peaks_lds(const tdoa_kparams &kp, bool is_float);
+bool tdoa_peaks_fits(const tdoa_kparams &kp, bool is_float);
+int tdoa_launch_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const void *scores,
+                      bool is_float, int64_t B, int num_peaks, int radius, float min_rel,
+                      void *stream);
 size_t tdoa_stream_trigger_lds(int M, int N, int H);
 // *by_id: the launch wrote each triggered frame at its stream's index
 // (k_stream_trigger_p) instead of its compact slot -- the layout DIRECT reads

@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 #include "tdoa_internal.h"
 
 int tdoa_set_error(int code, const char *msg);
@@ -26,14 +28,17 @@ __device__ __forceinline__ double ls_tau(const T *s, int K, int best)
 }
 
 // MM: the mic count at compile time, so the per-frame arrays (P sub-sample
-// lags, M distances and their derivatives) are registers, not scratch
-template <typename T, int MM>
+// lags, M distances and their derivatives) are registers, not scratch.
+// PEAKS (tdoa_peaks): row f is one of per_frame peaks of score frame
+// f / per_frame, its lags the peak's lag tuple; an empty slot (cell < 0) gets
+// NaN.
+template <typename T, int MM, bool PEAKS>
 __global__ void __launch_bounds__(128) k_ls(tdoa_kparams kp, const T *__restrict__ scores,
                                             const float *__restrict__ peak3,
                                             const int32_t *__restrict__ lags,
                                             const int32_t *__restrict__ cells,
                                             float *__restrict__ xy_ls, float *__restrict__ rms_out,
-                                            int64_t B, int iters)
+                                            int64_t B, int iters, int per_frame)
 {
     const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= B)
@@ -41,7 +46,21 @@ __global__ void __launch_bounds__(128) k_ls(tdoa_kparams kp, const T *__restrict
     constexpr int M = MM, P = MM * (MM - 1) / 2;
     const int K = kp.K;
     double tau[P];
-    if (peak3) {
+    if constexpr (PEAKS) {
+        if (cells[f] < 0) {
+            if (xy_ls) {
+                xy_ls[2 * f] = NAN;
+                xy_ls[2 * f + 1] = NAN;
+            }
+            if (rms_out)
+                rms_out[f] = NAN;
+            return;
+        }
+        const T *sf = scores + (size_t)(f / per_frame) * P * K;
+#pragma unroll
+        for (int p = 0; p < P; p++)
+            tau[p] = ls_tau(sf + (size_t)p * K, K, lags[f * P + p]);
+    } else if (peak3) {
         // the sub-sample lags from the peaks' scores: every lag and peak word
         // loaded before the first use (the branch inside the loop made each
         // pair's loads a round trip of their own)
@@ -127,7 +146,7 @@ __global__ void __launch_bounds__(128) k_ls(tdoa_kparams kp, const T *__restrict
 
 int tdoa_launch_ls(const tdoa_kparams &kp, const void *scores, bool is_float, const float *peak3,
                    const int32_t *lags, const int32_t *cells, float *xy_ls, float *rms,
-                   int64_t B, void *stream)
+                   int64_t B, void *stream, int per_frame)
 {
     if (B <= 0)
         return 0;
@@ -136,17 +155,23 @@ int tdoa_launch_ls(const tdoa_kparams &kp, const void *scores, bool is_float, co
         return tdoa_set_error(-1, "ls: batch too large for one launch");
     if (!peak3 && !scores)
         return tdoa_set_error(-1, "ls: neither peak scores nor raw scores");
+    if (per_frame > 0 && (peak3 || !scores))
+        return tdoa_set_error(-1, "ls: per-peak rows read the score block");
     hipStream_t st = (hipStream_t)stream;
     const bool flt = is_float || peak3;
+#define TDOA_LS_K(TT, MM, PK)                                                                           \
+    hipLaunchKernelGGL((k_ls<TT, MM, PK>), dim3((unsigned)grid), dim3(128), 0, st, kp, (const TT *)scores, \
+                       peak3, lags, cells, xy_ls, rms, B, TDOA_LS_ITERS, per_frame)
 #define TDOA_LS_M(MM)                                                                                   \
     case MM:                                                                                            \
-        if (flt)                                                                                        \
-            hipLaunchKernelGGL((k_ls<float, MM>), dim3((unsigned)grid), dim3(128), 0, st, kp,          \
-                               (const float *)scores, peak3, lags, cells, xy_ls, rms, B, TDOA_LS_ITERS); \
+        if (per_frame > 0 && flt)                                                                       \
+            TDOA_LS_K(float, MM, true);                                                                 \
+        else if (per_frame > 0)                                                                         \
+            TDOA_LS_K(int64_t, MM, true);                                                               \
+        else if (flt)                                                                                   \
+            TDOA_LS_K(float, MM, false);                                                                \
         else                                                                                            \
-            hipLaunchKernelGGL((k_ls<int64_t, MM>), dim3((unsigned)grid), dim3(128), 0, st, kp,        \
-                               (const int64_t *)scores, peak3, lags, cells, xy_ls, rms, B,              \
-                               TDOA_LS_ITERS);                                                          \
+            TDOA_LS_K(int64_t, MM, false);                                                              \
         break
     switch (kp.M) {
         TDOA_LS_M(2);
@@ -160,6 +185,7 @@ int tdoa_launch_ls(const tdoa_kparams &kp, const void *scores, bool is_float, co
         return tdoa_set_error(-1, "ls: num_mics outside 2..8");
     }
 #undef TDOA_LS_M
+#undef TDOA_LS_K
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         char buf[256];

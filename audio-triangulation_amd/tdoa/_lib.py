@@ -28,7 +28,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_decay_us", "tdoa_get_window", "tdoa_get_mics", "tdoa_get_lut",
     "tdoa_get_prior", "tdoa_dpss_q15", "tdoa_last_error", "tdoa_abi_version", "tdoa_batch_kernel",
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
-    "tdoa_heatmap", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
+    "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy",
     # tdoa_reference_abi.h
     "microphones_init", "rolling_buffer_init", "rolling_buffer_push",
@@ -64,6 +64,20 @@ class Outputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "lags", "gate", "cell", "xy", "max_L", "max_Lf", "scores", "weighted",
         "scores_f", "weighted_f", "xy_ls", "ls_rms")]
+
+
+MAX_PEAKS = 8  # TDOA_MAX_PEAKS
+
+
+class PeaksParams(C.Structure):
+    """struct tdoa_peaks_params (include/tdoa.h)."""
+    _fields_ = [("num_peaks", C.c_int32), ("radius", C.c_int32), ("min_rel", C.c_float)]
+
+
+class PeaksOutputs(C.Structure):
+    """struct tdoa_peaks_outputs (include/tdoa.h): device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "count", "cell", "xy", "L", "Lf", "lags", "xy_ls", "ls_rms")]
 
 
 class StreamOutputs(C.Structure):
@@ -130,6 +144,7 @@ def load() -> C.CDLL:
     L.tdoa_batch_grid_fused.restype = C.c_int
     L.tdoa_gpu_clock_mhz.argtypes = [C.c_int, P, C.c_double, C.POINTER(C.c_double)]
     L.tdoa_heatmap.argtypes = [P, P, P, C.c_int, I64, P, P]
+    L.tdoa_peaks.argtypes = [P, P, C.c_int, I64, C.POINTER(PeaksParams), C.POINTER(PeaksOutputs), P]
     L.tdoa_stream_create.argtypes = [P, I32, I32, P, I64, C.c_int, C.POINTER(P)]
     L.tdoa_stream_step.argtypes = [P, C.POINTER(StreamOutputs), P]
     L.tdoa_stream_reset.argtypes = [P, P]

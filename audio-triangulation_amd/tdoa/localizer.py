@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Config, Outputs, check, load
+from ._lib import Config, Outputs, PeaksOutputs, PeaksParams, check, load
 
 
 def _ptr(t: torch.Tensor | None):
@@ -249,6 +249,50 @@ class Localizer:
         check(load().tdoa_heatmap(self._ctx, _ptr(weighted), _ptr(max_L), int(is_float), B,
                                   _ptr(out), C.c_void_p(st.cuda_stream)), "tdoa_heatmap")
         return out
+
+    def peaks(self, scores: torch.Tensor, num_peaks: int = 2, radius: int = 8,
+              min_rel: float = 0.0, ls: bool = False, stream=None) -> dict:
+        """Up to `num_peaks` maxima of L = sum_p scores_p[LUT_p] per frame, a
+        square of `radius` cells suppressed around each (tdoa_peaks).
+
+        scores: [B][P][K] int64 or float32 on the context's GPU -- raw scores
+        (`scores` / `scores_f`) to find several simultaneous sources, weighted
+        scores for the map the reference displays, or EMA scores.  Returns
+        count [B], cell [B][Kp] (-1 in empty slots), xy [B][Kp][2], L (int64)
+        or Lf (float32) [B][Kp], lags [B][Kp][P] and, with ls, xy_ls / ls_rms.
+        Asynchronous on `stream` (default: the current stream)."""
+        P, K, dev = self.dims.P, self.dims.K, self.torch_device
+        if scores.dtype not in (torch.int64, torch.float32):
+            raise ValueError(f"scores must be int64 or float32, got {scores.dtype}")
+        if scores.dim() != 3 or tuple(scores.shape[1:]) != (P, K):
+            raise ValueError(f"scores must be [B][{P}][{K}], got {tuple(scores.shape)}")
+        if scores.device != dev:
+            raise ValueError(f"scores must live on {dev}")
+        if not scores.is_contiguous():
+            raise ValueError("scores must be contiguous")
+        B, Kp = scores.shape[0], int(num_peaks)
+        is_float = scores.dtype == torch.float32
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        n = max(Kp, 0)
+        with torch.cuda.stream(st):
+            o = {"count": torch.empty(B, dtype=torch.int32, device=dev),
+                 "cell": torch.empty((B, n), dtype=torch.int32, device=dev),
+                 "xy": torch.empty((B, n, 2), dtype=torch.float32, device=dev),
+                 "Lf" if is_float else "L": torch.empty((B, n), dtype=scores.dtype, device=dev),
+                 "lags": torch.empty((B, n, P), dtype=torch.int32, device=dev)}
+            if ls:
+                o["xy_ls"] = torch.empty((B, n, 2), dtype=torch.float32, device=dev)
+                o["ls_rms"] = torch.empty((B, n), dtype=torch.float32, device=dev)
+        if B == 0:  # nothing to launch (and empty tensors have no address to pass)
+            return o
+        prm = PeaksParams(Kp, int(radius), float(min_rel))
+        s = PeaksOutputs()
+        for name, _ in PeaksOutputs._fields_:
+            t = o.get(name)
+            setattr(s, name, None if t is None else t.data_ptr())
+        check(load().tdoa_peaks(self._ctx, _ptr(scores), int(is_float), B, C.byref(prm),
+                                C.byref(s), C.c_void_p(st.cuda_stream)), "tdoa_peaks")
+        return o
 
     def cell_xy(self, cell: np.ndarray) -> np.ndarray:
         """((x - half_w)/scale, (half_h - y)/scale) of row-major cells, float32 as on device."""

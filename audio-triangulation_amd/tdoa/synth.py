@@ -39,6 +39,59 @@ def adc_frames(B: int, M: int, N: int, lut: np.ndarray, S: int, seed: int,
     return frames.contiguous(), cells, tau
 
 
+def multi_source_frames(B: int, M: int, N: int, lut: np.ndarray, S: int, seed: int,
+                        num_sources: int = 2, min_sep: int = 25, src_std=(40.0, 32.0),
+                        noise_std: float = 4.0, mean: float = 128.0,
+                        device: str | torch.device = "cpu", grid_W: int | None = None):
+    """Frames with `num_sources` simultaneous independent broadband sources,
+    built like adc_frames: source k sits at a random grid cell, at least
+    `min_sep` cells (Chebyshev) from every other source of its frame, and
+    reaches mic m delayed by the integer tau taken from the LUT; the sources
+    add, plus N(0, noise_std) noise, rounded and clipped to [0, 255].
+    src_std[k] is source k's level (the last entry repeats).  grid_W: the
+    grid's width in cells (default: lut's last axis if it is [P][H][W], else
+    a square grid).
+    Returns (frames int16 [B][M][N], cells int64 [B][num_sources],
+    tau int64 [B][num_sources][M])."""
+    dev = torch.device(device)
+    g = torch.Generator(device=dev)
+    g.manual_seed(int(seed))
+    P = lut.shape[0]
+    G = lut.reshape(P, -1).shape[1]
+    if grid_W is None:
+        grid_W = lut.shape[2] if lut.ndim == 3 else int(round(G ** 0.5))
+    assert G % grid_W == 0, "grid_W does not divide the LUT's cells"
+    lut_t = torch.as_tensor(lut.reshape(P, -1).astype(np.int64), device=dev)
+    cells = torch.zeros((B, num_sources), dtype=torch.int64, device=dev)
+    for k in range(num_sources):
+        todo = torch.ones(B, dtype=torch.bool, device=dev)
+        for _ in range(1000):
+            draw = torch.randint(0, G, (B,), generator=g, device=dev)
+            cells[:, k] = torch.where(todo, draw, cells[:, k])
+            todo = torch.zeros(B, dtype=torch.bool, device=dev)
+            for j in range(k):
+                dx = (cells[:, k] % grid_W - cells[:, j] % grid_W).abs()
+                dy = (cells[:, k] // grid_W - cells[:, j] // grid_W).abs()
+                todo |= torch.maximum(dx, dy) < min_sep
+            if not bool(todo.any()):
+                break
+        else:
+            raise ValueError("min_sep leaves no room for the sources on this grid")
+    tau = torch.zeros((B, num_sources, M), dtype=torch.int64, device=dev)
+    for m in range(1, M):
+        tau[:, :, m] = lut_t[m - 1][cells] - S  # pair (0, m) is index m-1
+    std = [float(src_std[min(k, len(src_std) - 1)]) for k in range(num_sources)]
+    pad = S + 1
+    x = torch.zeros((B, M, N), device=dev)
+    for k in range(num_sources):
+        src = torch.randn((B, N + 2 * pad), generator=g, device=dev) * std[k]
+        idx = torch.arange(N, device=dev).view(1, 1, N) + pad - tau[:, k].reshape(B, M, 1)
+        x = x + torch.gather(src.view(B, 1, -1).expand(B, M, -1), 2, idx)
+    x = x + torch.randn((B, M, N), generator=g, device=dev) * noise_std + mean
+    frames = torch.clamp(torch.round(x), 0, 255).to(torch.int16)
+    return frames.contiguous(), cells, tau
+
+
 def full_range_frames(B: int, M: int, N: int, seed: int, device="cpu") -> torch.Tensor:
     dev = torch.device(device)
     g = torch.Generator(device=dev)

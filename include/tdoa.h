@@ -150,6 +150,74 @@ int tdoa_average_batch(tdoa_ctx *ctx, int64_t S, int64_t *est,
 int tdoa_heatmap(tdoa_ctx *ctx, const void *weighted, const void *max_L, int is_float,
                  int64_t B, uint8_t *classes, void *stream);
 
+/* ---- Multiple sources: the top peaks of the likelihood map ----
+ * tdoa_localize_batch reports one cell per frame, the first row-major argmax
+ * of L(cell) = sum_p score_p[LUT_p(cell)].  tdoa_peaks reports up to
+ * num_peaks maxima of the same map by greedy suppression, per frame:
+ *   1. L[c] for every cell, in T = int64 or fp32, the pairs added in
+ *      ascending p, one add per pair (as tdoa_heatmap evaluates it);
+ *   2. up to num_peaks times: take the maximum L among the cells not yet
+ *      suppressed, ties to the lowest cell index.  Peak 0 is always reported.
+ *      Peak k >= 1 is reported only if a cell remains and, for min_rel > 0,
+ *      (double)L_k >= (double)min_rel * (double)L_0; the first peak that is
+ *      not reported ends the search.  Then every cell with |cx - px| <= radius
+ *      and |cy - py| <= radius is suppressed.
+ * With num_peaks = 1 on a localize call's weighted block the result is that
+ * call's cell / xy / max_L (max_Lf).
+ *
+ * scores is a device [B][P][K] block, int64 (is_float = 0) or float
+ * (is_float = 1).  Which block gives which meaning:
+ *   scores / scores_f      the raw correlations: every source keeps its own
+ *                          peak in every pair, so this is the block for
+ *                          several simultaneous sources;
+ *   weighted / weighted_f  after the Gaussian lag prior centred on each
+ *                          pair's best lag: the map the reference displays
+ *                          (vga_heatmap.h), with the strongest source
+ *                          emphasised and the others damped by the prior;
+ *   the EMA scores of tdoa_average_batch (int64): the time-averaged map.
+ * A context whose batch route solves the grid inside its first kernel
+ * (tdoa_batch_grid_fused) or keeps the scores on chip writes these blocks
+ * only when the caller requests them in tdoa_outputs.
+ * NaN float scores: which cells are reported is unspecified; every cell
+ * written is in range or -1.
+ *
+ * xy_ls / ls_rms: the least-squares refinement of tdoa_outputs started at
+ * each peak, with the peak's lag tuple LUT_p(cell) - S in place of the
+ * pairs' argmax lags: tau_p = lag_p + the parabolic vertex of the given
+ * score block at lag_p - 1 .. lag_p + 1 (none at the ends of the lag range
+ * or where the three scores have no maximum).
+ *
+ * Asynchronous on `stream`; no host synchronisation and no allocation once
+ * the context's scratch has grown (it is used when xy_ls / ls_rms are
+ * requested without lags).  As for every call that may use the context's
+ * scratch: one stream per context while a call is in flight. */
+#define TDOA_MAX_PEAKS 8
+
+typedef struct tdoa_peaks_params {
+    int32_t num_peaks;   /* Kp, 1..TDOA_MAX_PEAKS */
+    int32_t radius;      /* suppression half-width in cells, >= 0 (Chebyshev square) */
+    float   min_rel;     /* > 0: peak k >= 1 is kept only if (double)L_k >= (double)min_rel * (double)L_0;
+                            <= 0: no threshold */
+} tdoa_peaks_params;
+
+typedef struct tdoa_peaks_outputs {  /* device pointers; any may be NULL except cell */
+    int32_t *count;   /* [B] peaks found, 1..Kp */
+    int32_t *cell;    /* [B][Kp] row-major cell, -1 in slots >= count (required) */
+    float   *xy;      /* [B][Kp][2] as tdoa_outputs.xy; NaN in empty slots */
+    int64_t *L;       /* [B][Kp] is_float == 0: L at the peak; INT64_MIN in empty slots */
+    float   *Lf;      /* [B][Kp] is_float == 1: L at the peak; -inf in empty slots */
+    int32_t *lags;    /* [B][Kp][P] LUT_p(cell) - S: the peak's lag tuple; 0 in empty slots */
+    float   *xy_ls;   /* [B][Kp][2] least-squares refinement started at the peak; NaN in empty slots */
+    float   *ls_rms;  /* [B][Kp] NaN in empty slots */
+} tdoa_peaks_outputs;
+
+/* TDOA_ERR_INVALID: a NULL ctx / scores / prm / out / out->cell, B < 0,
+ * num_peaks outside 1..TDOA_MAX_PEAKS, radius < 0, B >= 2^31, or a
+ * grid whose L map plus one frame's scores exceed the kernel's 150 KiB of LDS
+ * ((P*K + G) * sizeof(T)).  B = 0 returns TDOA_OK without a launch. */
+int tdoa_peaks(tdoa_ctx *ctx, const void *scores, int is_float, int64_t B,
+               const tdoa_peaks_params *prm, const tdoa_peaks_outputs *out, void *stream);
+
 /* Host helper: decay of correlations.c:42-43 from integer-us timestamps. */
 float tdoa_decay_us(uint64_t now_us, uint64_t last_us);
 

@@ -191,6 +191,39 @@ extern "C" int tdoa_dpss_q15(int32_t n, double nw, int32_t *out)
     return TDOA_OK;
 }
 
+// Band mask over the bins f_k = k fs / 2N, k = 0..N, of the 2N-point spectrum
+// (include/tdoa.h): 1 inside [lo, hi], raised-cosine edges of width taper
+// outside, 0 elsewhere; double arithmetic, rounded once to float.
+extern "C" int tdoa_band_weights(int32_t N, int32_t fs, double lo_hz, double hi_hz, double taper_hz,
+                                 float *w)
+{
+    if (!w)
+        return fail(TDOA_ERR_INVALID, "tdoa_band_weights: NULL table");
+    if (N < 256 || N > 4096 || (N & (N - 1)))
+        return fail(TDOA_ERR_INVALID, "tdoa_band_weights: N %d must be a power of two in [256,4096]", (int)N);
+    if (fs <= 0 || !(lo_hz >= 0.0) || !(lo_hz < hi_hz) || !(hi_hz <= 0.5 * fs) || !(taper_hz >= 0.0) ||
+        !std::isfinite(taper_hz))
+        return fail(TDOA_ERR_INVALID, "tdoa_band_weights: need 0 <= lo < hi <= fs/2 and a finite taper >= 0");
+    std::vector<float> t((size_t)N + 1);
+    bool any = false;
+    for (int k = 0; k <= N; k++) {
+        const double f = (double)k * (double)fs / (2.0 * N);
+        double v = 0.0;
+        if (f >= lo_hz && f <= hi_hz)
+            v = 1.0;
+        else if (taper_hz > 0.0 && f > lo_hz - taper_hz && f < lo_hz)
+            v = 0.5 * (1.0 - std::cos(M_PI * (f - (lo_hz - taper_hz)) / taper_hz));
+        else if (taper_hz > 0.0 && f > hi_hz && f < hi_hz + taper_hz)
+            v = 0.5 * (1.0 + std::cos(M_PI * (f - hi_hz) / taper_hz));
+        t[k] = (float)v;
+        any |= t[k] != 0.0f;
+    }
+    if (!any)
+        return fail(TDOA_ERR_INVALID, "tdoa_band_weights: no bin of the band has a non-zero weight");
+    std::memcpy(w, t.data(), sizeof(float) * t.size());
+    return TDOA_OK;
+}
+
 // ------------------------------------------------------------ context
 struct tdoa_ctx {
     tdoa_config cfg;
@@ -237,6 +270,10 @@ struct tdoa_ctx {
     // a fixed chunk of frames' spectra that stays in L2 / MALL between passes
     void *d_spec = nullptr;
     size_t spec_bytes = 0;
+    // band-limited GCC_PHAT (tdoa_set_bin_weights): the table in force (empty:
+    // none) and its device copy, [N + 1] floats, kept once allocated
+    std::vector<float> bin_w;
+    float *d_bin_w = nullptr;
     tdoa_kparams kp;
 };
 
@@ -448,6 +485,8 @@ void free_device(tdoa_ctx *c)
     (void)hipFree(c->d_spec);
     c->d_spec = nullptr;
     c->spec_bytes = 0;
+    (void)hipFree(c->d_bin_w);
+    c->d_bin_w = nullptr;
     c->d_wscratch = nullptr;
     c->wscratch_bytes = 0;
     c->d_tw = nullptr;
@@ -1191,6 +1230,73 @@ extern "C" int tdoa_get_prior(const tdoa_ctx *c, float *scale)
     if (!c || !scale)
         return fail(TDOA_ERR_INVALID, "NULL");
     std::memcpy(scale, c->prior.data(), sizeof(float) * c->K);
+    return TDOA_OK;
+}
+
+// ---------------------------------------------------- band-limited GCC_PHAT
+extern "C" int tdoa_set_bin_weights(tdoa_ctx *ctx, const float *w)
+{
+    if (!ctx)
+        return fail(TDOA_ERR_INVALID, "tdoa_set_bin_weights: NULL ctx");
+    if (ctx->cfg.engine != TDOA_ENGINE_GCC_PHAT)
+        return fail(TDOA_ERR_INVALID, "tdoa_set_bin_weights: the context's engine is not GCC_PHAT");
+    if (!w) {  // back to the shape's own route; the scratch stays until tdoa_destroy
+        ctx->bin_w.clear();
+        ctx->kp.bin_w = nullptr;
+        ctx->kp.bin_lo = ctx->kp.bin_hi = 0;
+        return TDOA_OK;
+    }
+    const int n = ctx->N + 1;
+    int lo = -1, hi = -1;
+    for (int k = 0; k < n; k++) {
+        if (!std::isfinite(w[k]) || w[k] < 0.0f)
+            return fail(TDOA_ERR_INVALID, "tdoa_set_bin_weights: w[%d] is negative or not finite", k);
+        if (w[k] != 0.0f) {
+            lo = lo < 0 ? k : lo;
+            hi = k;
+        }
+    }
+    if (lo < 0)
+        return fail(TDOA_ERR_INVALID, "tdoa_set_bin_weights: every weight is zero");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_spec) {  // shapes whose own route needs no spectrum scratch
+        const size_t want = (size_t)128 << 20;
+        if (hipMalloc(&ctx->d_spec, want) != hipSuccess) {
+            ctx->d_spec = nullptr;
+            return fail(TDOA_ERR_NOMEM, "GCC_PHAT spectrum scratch of %zu bytes", want);
+        }
+        ctx->spec_bytes = want;
+    }
+    if (!ctx->d_bin_w && hipMalloc(&ctx->d_bin_w, sizeof(float) * n) != hipSuccess) {
+        ctx->d_bin_w = nullptr;
+        return fail(TDOA_ERR_NOMEM, "tdoa_set_bin_weights: weight table of %d floats", n);
+    }
+    // no call of the context is in flight (include/tdoa.h): nothing reads d_bin_w now
+    HIP_TRY(hipMemcpy(ctx->d_bin_w, w, sizeof(float) * n, hipMemcpyHostToDevice));
+    ctx->bin_w.assign(w, w + n);
+    ctx->kp.bin_w = ctx->d_bin_w;
+    ctx->kp.bin_lo = lo;
+    ctx->kp.bin_hi = hi;
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_set_band_hz(tdoa_ctx *ctx, double lo_hz, double hi_hz, double taper_hz)
+{
+    if (!ctx)
+        return fail(TDOA_ERR_INVALID, "tdoa_set_band_hz: NULL ctx");
+    std::vector<float> w((size_t)ctx->N + 1);
+    const int rc = tdoa_band_weights(ctx->N, ctx->cfg.sample_rate_hz, lo_hz, hi_hz, taper_hz, w.data());
+    return rc ? rc : tdoa_set_bin_weights(ctx, w.data());
+}
+
+extern "C" int tdoa_get_bin_weights(const tdoa_ctx *c, float *w)
+{
+    if (!c || !w)
+        return fail(TDOA_ERR_INVALID, "NULL");
+    if (c->bin_w.empty())
+        std::fill(w, w + c->N + 1, 1.0f);
+    else
+        std::memcpy(w, c->bin_w.data(), sizeof(float) * c->bin_w.size());
     return TDOA_OK;
 }
 

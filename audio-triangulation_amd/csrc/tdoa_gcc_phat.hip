@@ -712,9 +712,13 @@ bool tdoa_gcc_phat_fused_grid(const tdoa_kparams &kp);
 
 // The one dispatch decision of tdoa_launch_gcc_phat, shared with
 // tdoa_gcc_phat_kernel_name so the reported kernel is the launched one.
-enum class PhatRoute { W64, P1K_LEAN, R16, SPLIT, FUSED_1024, GENERIC };
+enum class PhatRoute { BAND, W64, P1K_LEAN, R16, SPLIT, FUSED_1024, GENERIC };
 static PhatRoute phat_route(const tdoa_kparams &kp)
 {
+    // a weight table (tdoa_set_bin_weights): every shape takes the two-pass
+    // kernels with the weighted pass 2 (k_phat_spectra, k_phat_pairs_w)
+    if (kp.bin_w)
+        return PhatRoute::BAND;
     if (use_w64(kp))
         return PhatRoute::W64;
     if (tdoa_phat1024_fits(kp))
@@ -731,6 +735,8 @@ static PhatRoute phat_route(const tdoa_kparams &kp)
 const char *tdoa_gcc_phat_kernel_name(const tdoa_kparams &kp)
 {
     switch (phat_route(kp)) {
+    case PhatRoute::BAND:
+        return "k_phat_spectra";
     case PhatRoute::W64:
         return "k_p1k_w64";
     case PhatRoute::P1K_LEAN:
@@ -756,13 +762,18 @@ bool tdoa_frame16_fused_grid(const tdoa_kparams &kp);
 bool tdoa_gcc_phat_grid_in_kernel(const tdoa_kparams &kp)
 {
     const PhatRoute r = phat_route(kp);
+    if (r == PhatRoute::BAND)
+        return false;  // weighted scores through the context's scratch, then tdoa_launch_grid
     if (r == PhatRoute::R16)
         return tdoa_frame16_fused_grid(kp);
     return !tdoa_gcc_phat_needs_split(kp.M, kp.N) && tdoa_gcc_phat_fused_grid(kp);
 }
 
 // the launch writes the least-squares peak scores (kout.peak3) itself
-bool tdoa_gcc_phat_peak3(const tdoa_kparams &kp) { return tdoa_phat_r16_peak3(kp); }
+bool tdoa_gcc_phat_peak3(const tdoa_kparams &kp)
+{
+    return phat_route(kp) != PhatRoute::BAND && tdoa_phat_r16_peak3(kp);
+}
 
 // the N = 1024, M = 3 kernels (k_p1k_lean, k_gcc_phat_1024) solve the grid
 bool tdoa_gcc_phat_fused_grid(const tdoa_kparams &kp)
@@ -796,7 +807,7 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return tdoa_launch_phat1024(kp, out, frames, B, phat_eps, stream);
     if (route == PhatRoute::R16)
         return tdoa_launch_phat_r16(kp, out, frames, B, phat_eps, spec_scratch, spec_bytes, stream);
-    if (route == PhatRoute::SPLIT)
+    if (route == PhatRoute::SPLIT || route == PhatRoute::BAND)
         return tdoa_launch_gcc_phat_split(kp, out, frames, B,
                                           eps * 1073741824.0f /* 2^30: int16 units */,
                                           spec_scratch, spec_bytes, stream);

@@ -142,6 +142,11 @@ struct tdoa_kparams {
     // least-squares refinement (tdoa_ls.hip)
     const float *mic_xy;       // [M][2] metres
     float fs, c, height;
+    // band-limited GCC-PHAT (tdoa_set_bin_weights): R_ij[k] *= bin_w[k], k = 0..N
+    // bins of the 2N-point spectrum; null: no weighting, the shape's own route.
+    // bin_lo / bin_hi: the first / last bin with a non-zero weight
+    const float *bin_w;        // [N + 1]
+    int32_t bin_lo, bin_hi;
 };
 
 struct tdoa_kout {

@@ -7,9 +7,9 @@
 See include/tdoa.h for the C ABI and DESIGN.md for the kernels.
 """
 from ._lib import (ENGINE_DIRECT, ENGINE_GCC_PHAT, EXPORTED_SYMBOLS, LIB_PATH,  # noqa: F401
-                   TdoaError, decay_us, dpss_q15, load)
+                   TdoaError, band_weights, decay_us, dpss_q15, load)
 
-__all__ = ["Localizer", "TdoaError", "load", "dpss_q15", "decay_us"]
+__all__ = ["Localizer", "TdoaError", "load", "dpss_q15", "decay_us", "band_weights"]
 
 
 def __getattr__(name):

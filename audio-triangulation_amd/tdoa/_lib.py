@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy",
+    "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     # tdoa_reference_abi.h
     "microphones_init", "rolling_buffer_init", "rolling_buffer_push",
     "rolling_buffer_write_out", "rolling_buffer_get_incoming_power",
@@ -150,6 +151,10 @@ def load() -> C.CDLL:
     L.tdoa_stream_reset.argtypes = [P, P]
     L.tdoa_stream_state.argtypes = [P, P, P, P, P]
     L.tdoa_stream_destroy.argtypes = [P]
+    L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
+    L.tdoa_set_bin_weights.argtypes = [P, P]
+    L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]
+    L.tdoa_get_bin_weights.argtypes = [P, P]
     # reference-named per-frame symbols
     L.microphones_init.argtypes = []
     L.rolling_buffer_init.argtypes = [C.POINTER(RollingBuffer)]
@@ -181,6 +186,17 @@ def dpss_q15(n: int, nw: float = 2.0):
     out = np.zeros(n, np.int32)
     check(load().tdoa_dpss_q15(n, nw, out.ctypes.data_as(C.c_void_p)), "tdoa_dpss_q15")
     return out
+
+
+def band_weights(N: int, fs: int, lo: float, hi: float, taper: float = 0.0):
+    """Band mask float32 [N + 1] over the bins k * fs / 2N of the 2N-point
+    spectrum (tdoa_band_weights): 1 in [lo, hi] Hz, raised-cosine edges of
+    `taper` Hz outside, 0 elsewhere.  Host only."""
+    import numpy as np
+    w = np.zeros(max(int(N), 0) + 1, np.float32)
+    check(load().tdoa_band_weights(int(N), int(fs), float(lo), float(hi), float(taper),
+                                   w.ctypes.data_as(C.c_void_p)), "tdoa_band_weights")
+    return w
 
 
 def decay_us(now_us: int, last_us: int) -> float:

@@ -47,7 +47,8 @@ class Localizer:
                  engine: str = "direct", mic_xy=None, grid_half_w: int = 50,
                  grid_half_h: int = 50, grid_scale: float = 24.0,
                  height_offset: float = 1.2, speed_of_sound: float = 343.0,
-                 window_q15=None, phat_eps: float = 1e-12, device: int = 0):
+                 window_q15=None, phat_eps: float = 1e-12, device: int = 0,
+                 band_hz=None, band_taper_hz: float = 0.0):
         L = load()
         cfg = Config()
         L.tdoa_config_default(C.byref(cfg))
@@ -84,6 +85,12 @@ class Localizer:
         self.dims = Geometry(*[x.value for x in d])
         self.grid_W = 2 * grid_half_w + 1
         self.grid_half_w, self.grid_half_h, self.grid_scale = grid_half_w, grid_half_h, grid_scale
+        if band_hz is not None:
+            try:
+                self.set_band(band_hz[0], band_hz[1], band_taper_hz)
+            except Exception:
+                self.close()
+                raise
 
     # ---------------------------------------------------------- lifetime
     def close(self):
@@ -125,6 +132,31 @@ class Localizer:
         p = np.zeros(self.dims.K, np.float32)
         check(load().tdoa_get_prior(self._ctx, p.ctypes.data_as(C.c_void_p)), "tdoa_get_prior")
         return p
+
+    # ---------------------------------------------------------- band limiting
+    def set_band(self, lo: float, hi: float, taper: float = 0.0) -> None:
+        """Band-limited GCC-PHAT (tdoa_set_band_hz): only the bins in [lo, hi] Hz,
+        with raised-cosine edges of `taper` Hz, vote.  Synchronous; not while
+        a call of this context is in flight."""
+        check(load().tdoa_set_band_hz(self._ctx, float(lo), float(hi), float(taper)), "tdoa_set_band_hz")
+
+    def set_bin_weights(self, w) -> None:
+        """Per-bin weights float [N + 1] on the cross spectrum, finite and >= 0
+        (tdoa_set_bin_weights); None clears the table and the context runs its
+        unweighted kernels again.  Synchronous; not while a call is in flight."""
+        if w is None:
+            check(load().tdoa_set_bin_weights(self._ctx, None), "tdoa_set_bin_weights")
+            return
+        a = np.ascontiguousarray(w, dtype=np.float32).reshape(-1)
+        if a.size != self.dims.N + 1:
+            raise ValueError(f"bin weights must be [{self.dims.N + 1}], got {a.size}")
+        check(load().tdoa_set_bin_weights(self._ctx, a.ctypes.data_as(C.c_void_p)), "tdoa_set_bin_weights")
+
+    def bin_weights(self) -> np.ndarray:
+        """The table in force, float32 [N + 1]; all ones when none is set."""
+        w = np.zeros(self.dims.N + 1, np.float32)
+        check(load().tdoa_get_bin_weights(self._ctx, w.ctypes.data_as(C.c_void_p)), "tdoa_get_bin_weights")
+        return w
 
     # ---------------------------------------------------------- compute
     def alloc_outputs(self, B: int, scores: bool = False, grid: bool = True,

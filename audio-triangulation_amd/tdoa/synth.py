@@ -92,6 +92,44 @@ def multi_source_frames(B: int, M: int, N: int, lut: np.ndarray, S: int, seed: i
     return frames.contiguous(), cells, tau
 
 
+def interferer_frames(B: int, M: int, N: int, fs: int, S: int, seed: int, target_lags,
+                      interferer_lags, target_band=(1500, 5500), interferer_band=(12000, 24000),
+                      amp: float = 40, noise: float = 2, device: str | torch.device = "cpu"):
+    """A band-limited target under a band-limited interferer of the same level
+    (the band-limited GCC-PHAT scenario).  Per frame two independent Gaussian
+    noise signals of N + 4S samples are band-limited in the frequency domain
+    (bins of the (N + 4S)-point rfft outside the band zeroed) and scaled to unit
+    variance; mic m reads the target delayed by the integer target_lags[m] and
+    the interferer by interferer_lags[m] (|lag| <= 2S), each times `amp`, plus
+    N(0, noise) white noise, offset by 128, rounded and clipped to [0, 255].
+    Draw order (numpy default_rng(seed)): target [B][N + 4S], interferer
+    [B][N + 4S], white noise [B][M][N].
+    Returns (frames int16 [B][M][N] on `device`, target pair lags int32 [P],
+    interferer pair lags int32 [P]); pair (i, j) in lexicographic order has lag
+    lags[j] - lags[i], the sign of the engines' best lags."""
+    rng = np.random.default_rng(int(seed))
+    T, pad = N + 4 * S, 2 * S
+    f = np.arange(T // 2 + 1) * (float(fs) / T)
+
+    def band_noise(band):
+        X = np.fft.rfft(rng.standard_normal((B, T)), axis=-1)
+        X[:, (f < band[0]) | (f > band[1])] = 0.0
+        x = np.fft.irfft(X, T, axis=-1)
+        return x / x.std(axis=-1, keepdims=True)
+
+    sig = [band_noise(target_band), band_noise(interferer_band)]
+    lags = [np.asarray(target_lags, np.int64)[:M], np.asarray(interferer_lags, np.int64)[:M]]
+    x = rng.standard_normal((B, M, N)) * float(noise) + 128.0
+    n = np.arange(N)
+    for s, lag in zip(sig, lags):
+        assert lag.size == M and np.abs(lag).max() <= pad, "one lag per mic, |lag| <= 2S"
+        for m in range(M):
+            x[:, m] += float(amp) * s[:, pad + n - lag[m]]
+    frames = torch.from_numpy(np.clip(np.rint(x), 0, 255).astype(np.int16)).to(torch.device(device))
+    pair = [np.array([lag[j] - lag[i] for i in range(M) for j in range(i + 1, M)], np.int32) for lag in lags]
+    return frames.contiguous(), pair[0], pair[1]
+
+
 def full_range_frames(B: int, M: int, N: int, seed: int, device="cpu") -> torch.Tensor:
     dev = torch.device(device)
     g = torch.Generator(device=dev)

@@ -218,6 +218,49 @@ typedef struct tdoa_peaks_outputs {  /* device pointers; any may be NULL except 
 int tdoa_peaks(tdoa_ctx *ctx, const void *scores, int is_float, int64_t B,
                const tdoa_peaks_params *prm, const tdoa_peaks_outputs *out, void *stream);
 
+/* ---- Band-limited GCC_PHAT: per-bin weights on the cross spectrum ----
+ * PHAT gives every bin of the 2N-point spectrum the same vote whatever its
+ * energy, so a source that occupies part of the band loses to anything
+ * broadband elsewhere in it.  A weight table w[0..N] (real, finite, >= 0; bin k
+ * is f_k = k * fs / 2N) changes the definition to
+ *     R_ij[k] = w[k] * conj(U_i[k]) U_j[k],   r_ij = irfft(R_ij, 2N)
+ * and nothing else: lags, prior, gate, grid, least squares, heat map and
+ * tdoa_peaks are defined on these scores as before.  There is no
+ * renormalisation: a band that keeps a fraction q of the bins scales the peak
+ * of a clean delay, and with it max_Lf and the peak values, to about q
+ * (min_rel of tdoa_peaks is relative and unaffected).
+ *
+ * While a table is set, a tdoa_localize_batch of the context runs the two-pass
+ * kernels (k_phat_spectra, then k_phat_pairs_w) for every shape, through a
+ * spectrum scratch of the context: tdoa_batch_kernel names the first of them
+ * and tdoa_batch_grid_fused returns 0 -- one stream per context while a call
+ * is in flight.  Without a table (never set, or cleared with NULL) the context
+ * runs exactly the kernels, and computes exactly the bits, it does without
+ * this section.  tdoa_correlate_prepared runs the integer path on any context
+ * and the per-frame reference symbols (tdoa_reference_abi.h) have contexts of
+ * their own: neither is affected by a table. */
+
+/* Host only, no device: w[k] = 1 for lo <= f_k <= hi; with taper > 0 a raised
+ * cosine outside, 0.5 (1 - cos(pi (f_k - (lo - taper)) / taper)) for
+ * lo - taper < f_k < lo and 0.5 (1 + cos(pi (f_k - hi) / taper)) for
+ * hi < f_k < hi + taper; 0 elsewhere.  Double arithmetic, rounded to float.
+ * TDOA_ERR_INVALID unless 0 <= lo < hi <= fs/2, taper >= 0, N a power of two
+ * in 256..4096 and at least one bin gets a non-zero weight. */
+int tdoa_band_weights(int32_t N, int32_t fs, double lo_hz, double hi_hz, double taper_hz,
+                      float *w /* [N+1] */);
+/* Sets (w = host [N+1]) or clears (w = NULL) the context's table.
+ * Synchronous: copies the table to the device, and on first use allocates the
+ * spectrum scratch (128 MiB, as tdoa_create does for the two-pass shapes;
+ * freed by tdoa_destroy) if the context has none.  Must not be called while a
+ * call on the context is in flight.  TDOA_ERR_INVALID for a DIRECT context, a
+ * non-finite or negative entry, or an all-zero table; the table in force
+ * stays. */
+int tdoa_set_bin_weights(tdoa_ctx *ctx, const float *w);
+/* tdoa_band_weights with the context's N and fs, then tdoa_set_bin_weights. */
+int tdoa_set_band_hz(tdoa_ctx *ctx, double lo_hz, double hi_hz, double taper_hz);
+/* Host copy of the table in force; all 1.0f when none is set. */
+int tdoa_get_bin_weights(const tdoa_ctx *ctx, float *w /* [N+1] */);
+
 /* Host helper: decay of correlations.c:42-43 from integer-us timestamps. */
 float tdoa_decay_us(uint64_t now_us, uint64_t last_us);
 

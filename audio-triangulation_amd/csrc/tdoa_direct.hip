@@ -26,7 +26,6 @@
 
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 #ifdef TDOA_DIAG
 // Diagnostic build only (libtdoa_diag.so): per-workgroup phase stamps.

@@ -22,7 +22,6 @@
 #include "tdoa_fft32.h"
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 
@@ -677,17 +676,6 @@ __global__ void __launch_bounds__(192, 1) k_gcc_phat_1024(tdoa_kparams kp, tdoa_
 
 bool tdoa_gcc_phat_needs_split(int M, int N) { return M > 3 || N > 2048; }
 
-// the N = 1024, 3-mic kernel runs the grid solve itself (grid_tail)
-bool tdoa_phat1024_fits(const tdoa_kparams &kp);
-int tdoa_launch_phat1024(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames,
-                         int64_t B, float phat_eps, void *stream);
-
-#if TDOA_AB
-// one frame per 64-lane wave (tdoa_p1k_w64.hip, A/B build only)
-bool tdoa_p1k_w64_fits(const tdoa_kparams &kp);
-int tdoa_launch_p1k_w64(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames, int64_t B,
-                        float phat_eps, void *stream);
-#endif
 // config-2 kernel choice: TDOA_P1K=lean | w64 (A/B runs, A/B build), else the default
 static bool use_w64(const tdoa_kparams &kp)
 {
@@ -703,12 +691,6 @@ static bool use_w64(const tdoa_kparams &kp)
     return want && tdoa_p1k_w64_fits(kp);
 #endif
 }
-
-bool tdoa_phat_r16_fits(int M, int N, int S);
-bool frame16_shape(const tdoa_kparams &kp);
-const char *frame16_kernel_name(const tdoa_kparams &kp);
-
-bool tdoa_gcc_phat_fused_grid(const tdoa_kparams &kp);
 
 // The one dispatch decision of tdoa_launch_gcc_phat, shared with
 // tdoa_gcc_phat_kernel_name so the reported kernel is the launched one.
@@ -752,12 +734,7 @@ const char *tdoa_gcc_phat_kernel_name(const tdoa_kparams &kp)
     }
     return "k_gcc_phat";
 }
-int tdoa_launch_phat_r16(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames, int64_t B,
-                         float phat_eps, void *scratch, size_t scratch_bytes, void *stream);
 
-bool tdoa_phat_r16_peak3(const tdoa_kparams &kp);
-
-bool tdoa_frame16_fused_grid(const tdoa_kparams &kp);
 // the launch solves the grid itself (no weighted-score scratch, no grid launch)
 bool tdoa_gcc_phat_grid_in_kernel(const tdoa_kparams &kp)
 {

@@ -23,7 +23,6 @@
 #include "tdoa_internal.h"
 #include "tdoa_grid_bb.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 
@@ -228,7 +227,7 @@ __global__ void __launch_bounds__(bb_max_threads<TWC>()) BB_WPE k_grid_bb(tdoa_k
                         const int c = b + i * 64 + lane;
                         if (c < nch && P > 8) {
                             // many pairs: 16-B aligned chunks (rows KS apart, chunk
-                            // starts multiples of 4, tdoa_capi.cpp): one store; a
+                            // starts multiples of 4, tdoa_tables.cpp): one store; a
                             // last chunk's extra lags lie past every tuple's lag
                             *reinterpret_cast<v4u_t *>(reinterpret_cast<float *>(Wl) + (dsc[i] & 0xFFFFu)) = t[i];
                         } else if (c < nch) {

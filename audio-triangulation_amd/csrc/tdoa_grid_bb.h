@@ -4,7 +4,7 @@
 // (tdoa_stream.hip).  See DESIGN.md "k_grid_bb".
 //
 // The distinct tuples are regrouped by the 8 x 8 block of cells their first
-// cell lies in (entries of <= 64 tuples, host table, build_bb_tiles); an
+// cell lies in (entries of <= 64 tuples, host table, build_bb_tiles of tdoa_tables.cpp); an
 // entry's bound is the sum over pairs, in the pair order of L itself, of the
 // weighted-score maximum over the entry's lag range for that pair.  Addition
 // (float or int64) is monotone in each operand, so the bound is >= the L of
@@ -22,6 +22,7 @@
 #include <climits>
 #include <cmath>
 
+#include "tdoa_bb_layout.h"  // bb_row, bb_ks, bb_pk: shared with the host table builder
 #include "tdoa_fft32.h"
 #include "tdoa_internal.h"
 
@@ -133,15 +134,6 @@ __device__ __forceinline__ void wave_best(T &v, int &i)
     i = __builtin_amdgcn_readlane(i, 63);
 }
 
-// row stride of the grouped levels (P > 8): 8 lags per lane, 12 or 16 lanes
-__host__ __device__ constexpr int bb_row(int K) { return K <= 96 ? 96 : 128; }
-// row stride of the frame's scores in LDS: K, or K rounded up to 16 B for many
-// pairs (P > 8), whose level build then reads a lane's 16 scores as four
-// aligned 16-B reads and whose compact chunks expand by one 16-B store each
-__host__ __device__ constexpr int bb_ks(int P, int K) { return P > 8 ? (K + 3) & ~3 : K; }
-// the frame's scores per wave, padded to 16 B: the levels follow them
-__host__ __device__ constexpr int bb_pk(int P, int K) { return (P * bb_ks(P, K) + 3) & ~3; }
-
 // LDS scratch elements per wave after the frame's scores: the sparse table's
 // levels 1, 2, 3 [3][P][K] (P <= 8, bb_pk apart), or the same levels of four
 // pairs at a time [3][4][row] otherwise
@@ -153,7 +145,7 @@ __host__ __device__ constexpr int bb_scratch(int P, int K)
 // the level-j sparse table: S_j[i] = max w[i .. i + 2^j - 1], so the maximum
 // over a range of width n, 2^j <= n < 2^(j+1), is exactly
 // max(S_j[lo], S_j[hi + 1 - 2^j]) -- two independent reads.  The host encodes
-// every (entry, pair) range as that query (bb_query, tdoa_capi.cpp: offset of
+// every (entry, pair) range as that query (bb_query, tdoa_tables.cpp: offset of
 // the first window from the scores, distance of the second); a window never
 // crosses its pair's row, both lie inside [lo, hi].  Tables with a range wider
 // than 15 lags take the exhaustive k_grid (kp.bb_wide; configs 3 / 4: <= 11 / 15).

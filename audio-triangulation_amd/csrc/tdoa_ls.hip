@@ -14,7 +14,6 @@
 
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 

@@ -24,7 +24,6 @@
 
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 

@@ -46,7 +46,6 @@
 #include "tdoa_cplx.h"
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 

@@ -41,7 +41,6 @@
 #include "tdoa_internal.h"
 #include "tdoa_keys.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 
@@ -645,7 +644,7 @@ __device__ __forceinline__ int f16_epi_pair(int t)
     return w < EW && p < P ? p : P;
 }
 
-// pairs in the host's lexicographic order (tdoa_capi.cpp): pair p = (i, j)
+// pairs in the host's lexicographic order (tdoa_tables.cpp): pair p = (i, j)
 template <int M>
 __host__ __device__ constexpr int pair_first(int p)
 {
@@ -2540,7 +2539,6 @@ bool frame16_shape(const tdoa_kparams &kp)
 {
     return (kp.N == 4096 && (kp.M == 3 || kp.M == 4)) || (kp.N == 2048 && (kp.M == 4 || kp.M == 8));
 }
-bool tdoa_phat_r16_fits(int M, int N, int S);
 // a grid-requesting launch of this shape solves the grid in k_frame16 (FG):
 // no weighted-score scratch and no k_grid_bb launch (tdoa_capi.cpp run_batch)
 bool tdoa_frame16_fused_grid(const tdoa_kparams &kp)

@@ -16,7 +16,6 @@
 #include "tdoa.h"
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 

@@ -38,10 +38,6 @@ void correlate(const int16_t *a, const int16_t *b, const float *prior, int64_t *
 void average(int64_t *est, const int64_t *fresh, float decay, int *best);
 }  // namespace tdoa_host
 
-int tdoa_ctx_device(const tdoa_ctx *c);
-int tdoa_launch_ref_buffer(int op, int16_t *buf, const int16_t *ring, int head, int64_t *power,
-                           const int16_t *window, int n, void *stream, int16_t *s1, int16_t *s2);
-
 point2d_t mic_a_location;
 point2d_t mic_b_location;
 point2d_t mic_c_location;

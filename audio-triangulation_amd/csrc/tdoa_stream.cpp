@@ -8,18 +8,33 @@
 //   two parities are two captured graphs.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
+#include <memory>
 
 #include "../../include/tdoa.h"
+#include "tdoa_devmem.h"
 #include "tdoa_internal.h"
 
-int tdoa_set_error(int code, const char *msg);
-const tdoa_kparams *tdoa_ctx_kparams(const tdoa_ctx *c);
-int tdoa_ctx_device(const tdoa_ctx *c);
-int tdoa_ctx_engine(const tdoa_ctx *c);
-int tdoa_ctx_rate(const tdoa_ctx *c);
+// a captured step graph and what it was captured for
+struct step_graph {
+    hipGraphExec_t exec = nullptr;
+    hipGraph_t graph = nullptr;
+    tdoa_stream_outputs out{};
+    hipStream_t stream = nullptr;
+    step_graph() = default;
+    step_graph(const step_graph &) = delete;
+    step_graph &operator=(const step_graph &) = delete;
+    ~step_graph() { drop(); }
+    void drop()
+    {
+        if (exec)
+            (void)hipGraphExecDestroy(exec);
+        if (graph)
+            (void)hipGraphDestroy(graph);
+        exec = nullptr;
+        graph = nullptr;
+    }
+};
 
 struct tdoa_stream {
     tdoa_ctx *ctx;
@@ -27,35 +42,13 @@ struct tdoa_stream {
     int64_t S;
     tdoa_kparams kp;
     tdoa_stream_params sp;
-    void *mem = nullptr;  // one allocation for all state
-    size_t mem_bytes = 0;
+    tdoa_devmem mem;  // one allocation for all state
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
-    // captured step graphs (one per counter parity) and what they were captured for
-    hipGraphExec_t exec[2] = {nullptr, nullptr};
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    tdoa_stream_outputs g_out[2]{};
-    hipStream_t g_stream[2] = {nullptr, nullptr};
+    step_graph g[2];  // one per counter parity; released before mem
 };
 
 namespace {
-
-int sfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return tdoa_set_error(code, buf);
-}
-
-#define S_TRY(expr)                                                            \
-    do {                                                                       \
-        hipError_t e_ = (expr);                                                \
-        if (e_ != hipSuccess)                                                  \
-            return sfail(TDOA_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 tdoa_stream_kout to_kout(const tdoa_stream_outputs *o)
 {
@@ -117,16 +110,6 @@ int enqueue_step(tdoa_stream *st, const tdoa_stream_outputs *out, hipStream_t s,
     return tdoa_launch_stream_update(sp, st->kp, to_kout(out), st->S, s);
 }
 
-void drop_graph(tdoa_stream *st, int par)
-{
-    if (st->exec[par])
-        (void)hipGraphExecDestroy(st->exec[par]);
-    if (st->graph[par])
-        (void)hipGraphDestroy(st->graph[par]);
-    st->exec[par] = nullptr;
-    st->graph[par] = nullptr;
-}
-
 }  // namespace
 
 extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
@@ -134,25 +117,25 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
                                   tdoa_stream **out)
 {
     if (!ctx || !out || !capture)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: NULL argument");
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: NULL argument");
     *out = nullptr;
     if (tdoa_ctx_engine(ctx) != TDOA_ENGINE_DIRECT)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: needs a DIRECT context");
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: needs a DIRECT context");
     const tdoa_kparams &kp = *tdoa_ctx_kparams(ctx);
     const int M = kp.M, N = kp.N, P = kp.P, K = kp.K;
     if (num_streams < 1)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: num_streams %d < 1", num_streams);
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: num_streams %d < 1", num_streams);
     if (hop < 1 || hop > N || hop > 4096)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: hop %d outside [1, frame_len]", hop);
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: hop %d outside [1, frame_len]", hop);
     if (capture_len < (int64_t)N + 2 * hop)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: capture_len %lld < frame_len + 2 hop",
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: capture_len %lld < frame_len + 2 hop",
                      (long long)capture_len);
     if (tdoa_stream_trigger_lds(M, N, hop) > 150 * 1024)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_create: (frame_len + hop) x mics too large");
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: (frame_len + hop) x mics too large");
     const int dev = tdoa_ctx_device(ctx);
-    S_TRY(hipSetDevice(dev));
+    HIP_TRY(hipSetDevice(dev));
 
-    tdoa_stream *st = new tdoa_stream();
+    auto st = std::make_unique<tdoa_stream>();
     st->ctx = ctx;
     st->device = dev;
     st->S = num_streams;
@@ -170,12 +153,9 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
                  o_end = take(S * 8), o_at = take(S * 8), o_frames = take(S * M * N), o_fresh = take(S * P * K * 8),
                  o_fl = take(S * P * 4), o_fg = take(S), o_est = take(S * P * K * 8),
                  o_last = take(S * 8), o_stats = take(16);
-    if (hipMalloc(&st->mem, off) != hipSuccess) {
-        delete st;
-        return sfail(TDOA_ERR_NOMEM, "tdoa_stream_create: %zu bytes of stream state", off);
-    }
-    st->mem_bytes = off;
-    char *b = (char *)st->mem;
+    if (st->mem.alloc(off) != hipSuccess)
+        return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_create: %zu bytes of stream state", off);
+    char *b = st->mem.get<char>();
     tdoa_stream_params &sp = st->sp;
     sp.M = M;
     sp.N = N;
@@ -197,20 +177,17 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.est = (int64_t *)(b + o_est);
     sp.last = (uint64_t *)(b + o_last);
     sp.stats = (int64_t *)(b + o_stats);
-    if (hipMemset(st->mem, 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-        (void)hipFree(st->mem);
-        delete st;
-        return sfail(TDOA_ERR_HIP, "tdoa_stream_create: clearing state failed");
-    }
-    *out = st;
+    if (hipMemset(st->mem.get<void>(), 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+        return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_create: clearing state failed");
+    *out = st.release();
     return TDOA_OK;
 }
 
 extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out, void *stream)
 {
     if (!st)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_step: NULL stream");
-    S_TRY(hipSetDevice(st->device));
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step: NULL stream");
+    HIP_TRY(hipSetDevice(st->device));
     hipStream_t s = (hipStream_t)stream;
     const int par = (int)(st->hop & 1);
     if (!st->use_graph || !s) {
@@ -226,9 +203,10 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
         return rc;
     }
     const tdoa_stream_outputs want = out ? *out : tdoa_stream_outputs{};
-    if (!st->exec[par] || st->g_stream[par] != s || std::memcmp(&want, &st->g_out[par], sizeof want) != 0) {
-        drop_graph(st, par);
-        S_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    step_graph &sg = st->g[par];
+    if (!sg.exec || sg.stream != s || std::memcmp(&want, &sg.out, sizeof want) != 0) {
+        sg.drop();
+        HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         const int rc = enqueue_step(st, out, s, par);
         hipGraph_t g = nullptr;
         const hipError_t ec = hipStreamEndCapture(s, &g);
@@ -238,18 +216,18 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
             return rc;
         }
         if (ec != hipSuccess)
-            return sfail(TDOA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
-        st->graph[par] = g;
-        S_TRY(hipGraphInstantiate(&st->exec[par], g, nullptr, nullptr, 0));
-        st->g_out[par] = want;
-        st->g_stream[par] = s;
+            return tdoa_fail(TDOA_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(ec));
+        sg.graph = g;
+        HIP_TRY(hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0));
+        sg.out = want;
+        sg.stream = s;
     }
-    const hipError_t el = hipGraphLaunch(st->exec[par], s);
+    const hipError_t el = hipGraphLaunch(sg.exec, s);
     if (el != hipSuccess) {
         // as in the eager path: a partly run hop may have counted into its
         // slot; both slots are zeroed so the next hop starts from slot 0
         (void)hipMemsetAsync(st->sp.count, 0, 2 * sizeof(int32_t), s);
-        return sfail(TDOA_ERR_HIP, "hipGraphLaunch: %s", hipGetErrorString(el));
+        return tdoa_fail(TDOA_ERR_HIP, "hipGraphLaunch: %s", hipGetErrorString(el));
     }
     st->hop++;
     return TDOA_OK;
@@ -258,9 +236,9 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
 extern "C" int tdoa_stream_reset(tdoa_stream *st, void *stream)
 {
     if (!st)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_reset: NULL stream");
-    S_TRY(hipSetDevice(st->device));
-    S_TRY(hipMemsetAsync(st->mem, 0, st->mem_bytes, (hipStream_t)stream));
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_reset: NULL stream");
+    HIP_TRY(hipSetDevice(st->device));
+    HIP_TRY(hipMemsetAsync(st->mem.get<void>(), 0, st->mem.bytes(), (hipStream_t)stream));
     st->hop = 0;  // both counter slots are zero again
     return TDOA_OK;
 }
@@ -269,19 +247,19 @@ extern "C" int tdoa_stream_state(tdoa_stream *st, int64_t *pos, int64_t *est, ui
                                  int64_t *stats)
 {
     if (!st)
-        return sfail(TDOA_ERR_INVALID, "tdoa_stream_state: NULL stream");
-    S_TRY(hipSetDevice(st->device));
-    S_TRY(hipDeviceSynchronize());
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state: NULL stream");
+    HIP_TRY(hipSetDevice(st->device));
+    HIP_TRY(hipDeviceSynchronize());
     const size_t S = (size_t)st->S;
     if (pos)
-        S_TRY(hipMemcpy(pos, st->sp.pos, sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(pos, st->sp.pos, sizeof(int64_t), hipMemcpyDeviceToHost));
     if (est)
-        S_TRY(hipMemcpy(est, st->sp.est, S * st->kp.P * st->kp.K * sizeof(int64_t),
+        HIP_TRY(hipMemcpy(est, st->sp.est, S * st->kp.P * st->kp.K * sizeof(int64_t),
                         hipMemcpyDeviceToHost));
     if (last)
-        S_TRY(hipMemcpy(last, st->sp.last, S * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(last, st->sp.last, S * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (stats)
-        S_TRY(hipMemcpy(stats, st->sp.stats, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(stats, st->sp.stats, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TDOA_OK;
 }
 
@@ -291,9 +269,6 @@ extern "C" int tdoa_stream_destroy(tdoa_stream *st)
         return TDOA_OK;
     (void)hipSetDevice(st->device);
     (void)hipDeviceSynchronize();
-    drop_graph(st, 0);
-    drop_graph(st, 1);
-    (void)hipFree(st->mem);
-    delete st;
+    delete st;  // the graphs, then the state
     return TDOA_OK;
 }

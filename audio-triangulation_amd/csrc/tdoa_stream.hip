@@ -33,7 +33,6 @@
 #include "tdoa_internal.h"
 #include "tdoa_keys.h"
 
-int tdoa_set_error(int code, const char *msg);
 
 namespace {
 

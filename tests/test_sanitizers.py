@@ -2,8 +2,10 @@
 
 `make -C audio-triangulation_amd sanitize` builds tdoa/libtdoa_san.so -- the whole
 library with its HOST code instrumented (tdoa_host_path.cpp's per-frame path,
-tdoa_reference_abi.cpp's capture ring and geometry, the context setup and table
-builders of tdoa_capi.cpp; device code is not, -fno-gpu-sanitize) -- and
+tdoa_reference_abi.cpp's capture ring and geometry, the table builders of
+tdoa_tables.cpp for the configs test_abi.py hands tdoa_create, which builds them
+before it asks for a device (tests/test_tables_cpu.py runs them under the
+sanitizers for every branch); device code is not, -fno-gpu-sanitize) -- and
 `make -C oracle sanitize` the oracle restatement.  Then, in a child process with
 clang's sanitizer runtime preloaded:
   * tests/test_ref_host_path.py, test_abi.py and test_reference_loop.py run

@@ -1,12 +1,11 @@
 // tdoa_phat1024.hip -- GCC-PHAT metric kernel for BASELINE config 2
 // (3 mics x 1024-sample frames, L = 2048), see DESIGN.md "k_phat1024".
 //
-// One frame per 32-lane half-wave; the three mics of the frame run in the same
-// lanes, so no spectrum ever crosses a wave and the kernel has no workgroup
-// barrier after the table staging.  The work of a frame is issued as two
-// independent FFT streams at a time (mic 0 | mic 1, pair (0,1) inverse | mic 2
-// forward, pair (0,2) | pair (1,2)), each with its own transpose tile, so one
-// wave per SIMD has the instruction-level parallelism to cover LDS latency.
+// One frame per 32-lane half-wave (two frames per wave); the three mics of the
+// frame run in the same lanes, so no spectrum ever crosses a wave and the
+// kernel has no workgroup barrier after the table staging.  A frame is one FFT
+// stream through the half-wave's own transpose tile; two waves per SIMD hide
+// each other's LDS round trips (k_p1k_lean<NW> below: NW waves per workgroup).
 //
 // Per mic m (rolling_buffer.c:64-66, buffer.c:13-16, buffer.c:4-11 front end):
 //   z[n] = x[2n] + i x[2n+1]  (n < 512; the upper half is the zero padding)
@@ -29,9 +28,9 @@
 //   swap back to residue columns, y = IFFT_1024(Y) pruned to the outputs
 //   n = n1 (+992) that hold lags -S..S, argmax + lag prior (correlations.c:20-33
 //   semantics on float scores), gate (sample_compute.h:124-134).
-// Per wave and two iterations: the grid solve of vga_heatmap.h:99-108 for its
-// four frames at once (lanes split the distinct lag tuples, one b128 gather per
-// pair reads the four frames' weighted scores).
+// Per wave: the grid solve of vga_heatmap.h:99-108 for its two frames at once
+// (lanes split the distinct lag tuples, one b64 gather per pair reads the two
+// frames' weighted scores from an [p][k] float2 table in the wave's tiles).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,6 +38,7 @@
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <type_traits>
 #include <vector>
@@ -46,6 +46,11 @@
 #include "tdoa_cplx.h"
 #include "tdoa_internal.h"
 
+// TDOA_AB=1: the A/B build (tdoa/libtdoa_ab.so) holds both workgroup shapes of
+// k_p1k_lean; the product holds the one it launches
+#ifndef TDOA_AB
+#define TDOA_AB 0
+#endif
 
 namespace {
 
@@ -54,8 +59,10 @@ constexpr int P1K_TILE = 32 * P1K_ROW;    // 8448 B: one transpose of one half-w
 constexpr int P1K_KPAD = 128;             // lag slots per pair in the grid score table
 constexpr int P1K_WAVE_LDS = 2 * P1K_TILE;  // a wave's two transpose tiles (one per half-wave)
 [[maybe_unused]] constexpr int P1K_GB = 8;               // grid tuples per lane per batch
-// LDS table image: twm [32][32] f2 | tw2 [16][32] f2 | win [512] f2 | prior [128] | tuples
-constexpr int P1K_IMG_FIXED = 32 * 32 * 8 + 16 * 32 * 8 + 512 * 8 + 128 * 4;
+// Table image: twm [32][32] f2 | tw2 [16][32] f2 | prior [128] | win [512] f2 | tuples.
+// The first P1K_IMG_LDS4 bytes are all that the 4-wave workgroup keeps in LDS.
+constexpr int P1K_IMG_LDS4 = 32 * 32 * 8 + 16 * 32 * 8 + 128 * 4;
+constexpr int P1K_IMG_FIXED = P1K_IMG_LDS4 + 512 * 8;
 
 // Tile row / column and table column of residue (or DFT index) x: 16 and 24
 // swap places, so the residues of every 16-lane group of a half-wave --
@@ -201,6 +208,22 @@ __device__ __forceinline__ f2 lds_f2(const char *base, int off)
 #ifndef P1K_LATE_STORES
 #define P1K_LATE_STORES 1
 #endif
+// The 4-wave workgroup's knobs (k_p1k_lean<4>; A/B variants, DESIGN.md has the figures):
+// P1K_WG4_PRIO=1: s_setprio 3 in the latency-bound phases (staging, grid), 0 in
+//   the transforms, instead of the default priority throughout
+#ifndef P1K_WG4_PRIO
+#define P1K_WG4_PRIO 0
+#endif
+// P1K_WG4_WQ_LATE=1: mic 2's window taps requested after pair (0,1)'s maximum
+//   instead of with the row's words (16 fewer live registers across it)
+#ifndef P1K_WG4_WQ_LATE
+#define P1K_WG4_WQ_LATE 0
+#endif
+// P1K_WG4_TUPS_ALL=1: every tuple word of the lane requested at the grid's
+//   start (the scan unrolled over at most 14 steps) instead of two steps ahead
+#ifndef P1K_WG4_TUPS_ALL
+#define P1K_WG4_TUPS_ALL 0
+#endif
 // plain LDS read (the grid's gathers: data-dependent addresses, never merged,
 // and free to be scheduled around the other reads of the software pipeline)
 __device__ __forceinline__ f2 lds_f2_plain(const char *base, int off)
@@ -301,10 +324,14 @@ struct NoHook {
     __device__ void operator()() const {}
 };
 
-template <typename Hook = NoHook>
-__device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)[16], f2 (&V)[33],
-                                              float e2, Hook after_front = Hook())
+// A row's words: the frame words w, and -- where the window is not in LDS
+// (WQ, the 4-wave workgroup) -- the window's Q15 tap pairs q from kp.window:
+// dword res + 32 t of either array covers samples 2 (res + 32 t), + 1.
+template <int NQ, typename Hook = NoHook>
+__device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
+                                              f2 (&V)[33], float e2, Hook after_front = Hook())
 {
+    constexpr bool WQ = NQ == 16;
     f2 v[32];
     {
         int s = 0;
@@ -316,8 +343,13 @@ __device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)
         const uint32_t off2 = off | (off << 16);
 #pragma unroll
         for (int t = 0; t < 16; t++) {
-            const f2 wf = lds_f2(L.win, 8 * L.cs + 256 * t);
             const uint32_t d = (w[t] | 0x01000100u) - off2;
+            f2 wf;
+            if constexpr (WQ) {  // the image's (float)W / 128, formed here (exact: W < 2^15)
+                const uint32_t q = wq[t];
+                wf = f2{(float)(int16_t)(q & 0xFFFFu), (float)(int16_t)(q >> 16)} * f2{1.0f / 128.0f, 1.0f / 128.0f};
+            } else
+                wf = lds_f2(L.win, 8 * L.cs + 256 * t);
             const float s0 = (float)(int8_t)(d & 0xFFu);
             const float s1 = (float)(int8_t)((d >> 16) & 0xFFu);
             const f2 pr = f2{s0, s1} * wf;  // one packed multiply
@@ -363,11 +395,11 @@ __device__ __forceinline__ void lean_split(const Lane &L, f2 A, f2 Bv, int k, fl
 }
 
 // unit spectrum of one mic row, in place (paired layout)
-template <typename Hook = NoHook>
-__device__ __forceinline__ void lean_forward(const Lane &L, const uint32_t (&w)[16], f2 (&U)[33],
-                                             float e2, Hook after_front = Hook())
+template <int NQ, typename Hook = NoHook>
+__device__ __forceinline__ void lean_forward(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
+                                             f2 (&U)[33], float e2, Hook after_front = Hook())
 {
-    lean_spectrum(L, w, U, e2, after_front);
+    lean_spectrum(L, w, wq, U, e2, after_front);
 #if P1K_TWPF & 1
     f2 wn = lean_tw2(L, 0);
 #pragma unroll
@@ -386,11 +418,12 @@ __device__ __forceinline__ void lean_forward(const Lane &L, const uint32_t (&w)[
 
 // unit spectrum V of one mic row consumed bin pair by bin pair as it is
 // produced: A <- conj(A) V, B <- conj(B) V (V is never whole after the split)
-__device__ __forceinline__ void lean_forward_cross(const Lane &L, const uint32_t (&w)[16],
+template <int NQ>
+__device__ __forceinline__ void lean_forward_cross(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
                                                    f2 (&A)[33], f2 (&Bs)[33], float e2)
 {
     f2 V[33];
-    lean_spectrum(L, w, V, e2);
+    lean_spectrum(L, w, wq, V, e2);
     A[32] = c_conjmul(A[32], V[32]);
     Bs[32] = c_conjmul(Bs[32], V[32]);
 #if P1K_TWPF & 2
@@ -509,18 +542,35 @@ __device__ __forceinline__ void lean_pretwiddle(const Lane &L, const f2 (&A)[33]
 
 }  // namespace
 
-__global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout out,
-                                                     const int16_t *__restrict__ frames, int64_t B,
-                                                     float e2)
+// NW waves per workgroup, 2 NW frames:
+//   NW = 8  (A/B: TDOA_P1K=lean8) one workgroup per CU, the whole table image in LDS, and the two
+//           waves of a SIMD (w, w ^ 4) kept in step by balance();
+//   NW = 4  (the product) two independent workgroups per CU (80 KiB of LDS each), usually of
+//           consecutive launches and so at different phases: one's staging and
+//           grid scan issue under the other's VALU-bound transforms.  LDS holds
+//           the tiles and the image's prefix twm | tw2 | prior; the window
+//           comes from kp.window with the row's words and the grid's tuple
+//           words from the image in global memory (L2), two steps ahead.
+// The per-frame arithmetic and its order are the same, so are all outputs.
+template <int NW>
+__global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout out,
+                                                         const int16_t *__restrict__ frames, int64_t B,
+                                                         float e2)
 {
-    constexpr int N = 1024, P = 3, NW = 8, NF = 2 * NW, NT = NW * 64;
+    static_assert(NW == 4 || NW == 8, "k_p1k_lean: 4 or 8 waves per workgroup");
+    constexpr int N = 1024, P = 3, NF = 2 * NW, NT = NW * 64;
+    constexpr bool WG4 = NW == 4;
+    static_assert(!WG4 || NW * P1K_WAVE_LDS + P1K_IMG_LDS4 <= 80 * 1024, "two workgroups must fit a CU's 160 KiB of LDS");
+    static_assert(!WG4 || !P1K_GROUPS, "the grouped scan reads its words from LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *tiles = smem;                               // [NW][2][TILE]
     char *twm = tiles + NW * 2 * P1K_TILE;            // [32][32] f2
     char *tw2 = twm + 32 * 32 * 8;                    // [16][32] f2
-    char *win = tw2 + 16 * 32 * 8;                    // [512] f2
-    const float *prior = (const float *)(win + 512 * 8);  // [128]
-    const uint32_t *tups = (const uint32_t *)(prior + 128);
+    const float *prior = (const float *)(tw2 + 16 * 32 * 8);  // [128]
+    char *win = (char *)(prior + 128);                // [512] f2 (NW = 8 only)
+    // the tuple words: after the window in LDS, or in the global image
+    const uint32_t *tups = WG4 ? (const uint32_t *)((const char *)kp.p1k_img + P1K_IMG_FIXED)
+                               : (const uint32_t *)(win + 512 * 8);
 
     const int tid = threadIdx.x, wave = tid >> 6, hw = (tid >> 5) & 1, lane64 = tid & 63;
 #ifdef TDOA_DIAG
@@ -545,25 +595,35 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
     // finishes its last ~9 us alone, with nothing to hide its latencies; here
     // a wave that has passed more phase boundaries than its partner drops to
     // the low priority until the partner catches up
-    __shared__ int prog[NW];
-    if (lane64 == 0)
-        prog[wave] = 0;
-    __builtin_amdgcn_s_setprio(2);
+    // (NW = 4 has none of this: a wave's SIMD partner belongs to another
+    // workgroup, and the default priority leaves the issue oldest-first)
+    __shared__ int prog[WG4 ? 1 : NW];
+    if constexpr (!WG4) {
+        if (lane64 == 0)
+            prog[wave] = 0;
+        __builtin_amdgcn_s_setprio(2);
+    }
+#if P1K_WG4_PRIO
+    if constexpr (WG4)
+        __builtin_amdgcn_s_setprio(3);
+#endif
     int phase = 0;
     auto balance = [&]() {
         // through an LDS-address-space pointer: ds_write / ds_read.  A generic
         // volatile pointer made them flat accesses, and the flat load's wait
         // (vmcnt(0) lgkmcnt(0)) also waited for the next mic's words in flight
 #if P1K_BALANCE
-        volatile __attribute__((address_space(3))) int *pv = (volatile __attribute__((address_space(3))) int *)prog;
-        ++phase;
-        if (lane64 == 0)
-            pv[wave] = phase;
-        const int other = __builtin_amdgcn_readfirstlane(pv[wave ^ 4]);
-        if (phase > other)
-            __builtin_amdgcn_s_setprio(0);
-        else
-            __builtin_amdgcn_s_setprio(2);
+        if constexpr (!WG4) {
+            volatile __attribute__((address_space(3))) int *pv = (volatile __attribute__((address_space(3))) int *)prog;
+            ++phase;
+            if (lane64 == 0)
+                pv[wave] = phase;
+            const int other = __builtin_amdgcn_readfirstlane(pv[wave ^ 4]);
+            if (phase > other)
+                __builtin_amdgcn_s_setprio(0);
+            else
+                __builtin_amdgcn_s_setprio(2);
+        }
 #endif
     };
     Lane L;
@@ -585,28 +645,40 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
     const int Upad = (kp.U + P1K_GB * 64 - 1) / (P1K_GB * 64) * (P1K_GB * 64);
 #endif
 
-    auto fetch = [&](uint32_t(&w)[16], int64_t fr, int m) {
+    constexpr int NQ = WG4 ? 16 : 1;  // (NW = 8: one unused word)
+    auto fetch_win = [&](uint32_t(&q)[NQ]) {
+        if constexpr (WG4) {  // the window's taps of the same samples (L2 hits)
+            const uint32_t *wq = reinterpret_cast<const uint32_t *>(kp.window) + L.res;
+#pragma unroll
+            for (int t = 0; t < 16; t++)
+                q[t] = wq[32 * t];
+        }
+    };
+    auto fetch = [&](uint32_t(&w)[16], uint32_t(&q)[NQ], int64_t fr, int m, bool win = true) {
         const uint32_t *row = reinterpret_cast<const uint32_t *>(
             frames + ((fr < B ? fr : B - 1) * 3 + m) * (int64_t)N) + L.res;
 #pragma unroll
         for (int t = 0; t < 16; t++)
             w[t] = __builtin_nontemporal_load(row + 32 * t);
+        if (win)
+            fetch_win(q);
     };
     // table image: its loads first (L2 hits), then the first frames' words
     // (HBM), then the image's LDS writes -- the frames' latency overlaps the
     // staging instead of following it
     uint32_t w0[16], w1[16];
+    [[maybe_unused]] uint32_t q0[NQ] = {}, q1[NQ] = {};
     {
         const uint4 *src = (const uint4 *)kp.p1k_img;
         uint4 *dst = (uint4 *)twm;
-        const int n16 = do_grid ? kp.p1k_img_bytes / 16 : P1K_IMG_FIXED / 16;
+        const int n16 = WG4 ? P1K_IMG_LDS4 / 16 : (do_grid ? kp.p1k_img_bytes / 16 : P1K_IMG_FIXED / 16);
         constexpr int SR = 4;  // image <= SR * NT * 16 B = 32 KiB (tdoa_phat1024_fits)
         uint4 img[SR];
 #pragma unroll
         for (int r = 0; r < SR; r++)  // unconditional (clamped) loads: straight-line
             img[r] = src[tid + r * NT < n16 ? tid + r * NT : n16 - 1];  // code, counted waits
         const int64_t f = (int64_t)blockIdx.x * NF + 2 * wave + hw;
-        fetch(w0, f, 0);
+        fetch(w0, q0, f, 0);
 #pragma unroll
         for (int r = 0; r < SR; r++)  // unconditional too (a clamped index rewrites
             dst[tid + r * NT < n16 ? tid + r * NT : n16 - 1] = img[r];  // the last unit)
@@ -614,19 +686,29 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
     __syncthreads();
     // keep the first row's use (and its wait) below the barrier: hoisted above
     // it, every wave of the workgroup would wait for the latest wave's row
+#if P1K_WG4_PRIO
+    if constexpr (WG4)
+        __builtin_amdgcn_s_setprio(0);
+#endif
 #pragma unroll
     for (int t = 0; t < 16; t++)
         asm volatile("" : "+v"(w0[t]));
+    if constexpr (WG4) {
+#pragma unroll
+        for (int t = 0; t < 16; t++)
+            asm volatile("" : "+v"(q0[t]));
+    }
 
     const float invL = 1.0f / 2048.0f;
 
-    // one iteration per workgroup (grid = ceil(B / 16)): no value lives across
+    // one iteration per workgroup (grid = ceil(B / NF)): no value lives across
     // a loop back-edge, which the register allocator answered with spills
     {
         const int64_t base = (int64_t)blockIdx.x * NF;
         const int64_t f = base + 2 * wave + hw;
         const bool live = f < B;
         uint32_t w2[16];
+        [[maybe_unused]] uint32_t q2[NQ] = {};
         LEAN_MARK();
         float wv[3][4];
         int best[3];
@@ -652,7 +734,7 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
             half_argmax_key(bkey, bk);  // every lane of the half-wave
             bk = bk < 0 ? 0 : (bk >= K ? K - 1 : bk);
             best[p] = bk - S;
-            const int64_t ff = base + 2 * ((ft >> 6) & 7) + fhw;
+            const int64_t ff = base + 2 * ((ft >> 6) & (NW - 1)) + fhw;
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 const int d = ck[c] > bk ? ck[c] - bk : bk - ck[c];
@@ -680,19 +762,19 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
         // the mics' rows are requested one at a time, each after the previous
         // one's front end: at the kernel's start the memory system serves every
         // wave's first row (8 MB) instead of all rows at once
-        lean_forward(L, w0, U0, e2, [&] {
-            fetch(w1, f, 1);
+        lean_forward(L, w0, q0, U0, e2, [&] {
+            fetch(w1, q1, f, 1);
             balance();
         });
         LEAN_MARK();
         balance();
 #if P1K_W2_EARLY
-        lean_forward(L, w1, U1, e2, [&] {
-            fetch(w2, f, 2);
+        lean_forward(L, w1, q1, U1, e2, [&] {
+            fetch(w2, q2, f, 2);
             balance();
         });
 #else
-        lean_forward(L, w1, U1, e2, [&] { balance(); });
+        lean_forward(L, w1, q1, U1, e2, [&] { balance(); });
 #endif
         LEAN_MARK();
         balance();
@@ -703,14 +785,17 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
 #if !P1K_W2_EARLY
             // mic 2's words: fetched after the pair's column pass, the kernel's
             // register peak (two unit spectra + a working column)
-            fetch(w2, f, 2);
+            fetch(w2, q2, f, 2, !P1K_WG4_WQ_LATE);
 #endif
             lean_row_inv(L, L.tileA, y0, y31);
         }
         finish_pair(0, y0, y31);
+#if P1K_WG4_WQ_LATE
+        fetch_win(q2);
+#endif
         LEAN_MARK();
         balance();
-        lean_forward_cross(L, w2, U0, U1, e2);  // pairs 1: (0, 2), 2: (1, 2)
+        lean_forward_cross(L, w2, q2, U0, U1, e2);  // pairs 1: (0, 2), 2: (1, 2)
         LEAN_MARK();
         balance();
         {
@@ -736,6 +821,20 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
         // grid's one global load (the winner's first cell) waits in issue
         // order: behind these stores it waited for their HBM write acks
         auto store_frame = [&]() {
+            if constexpr (WG4) {
+                // the frame index from the lane id again (fresh_tid): held from
+                // the kernel's start it cost the register that spilled
+                const int ft = fresh_tid();
+                const int64_t fq = base + 2 * ((ft >> 6) & (NW - 1)) + ((ft >> 5) & 1);
+                if (fq < B && (ft & 31) == 0) {
+#pragma unroll
+                    for (int p = 0; p < 3; p++)
+                        out.lags[fq * P + p] = best[p];
+                    if (out.gate)
+                        out.gate[fq] = best[0] * best[0] + best[1] * best[1] + best[2] * best[2] > 4 ? 1 : 0;
+                }
+                return;
+            }
             if (live && L.lane == 0) {
 #pragma unroll
                 for (int p = 0; p < 3; p++)
@@ -757,6 +856,10 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
         // weighted scores [p][KPAD] f2 (frame hw in component hw) in the wave's
         // tile space, lanes split the distinct lag tuples (4 consecutive per
         // lane and step, ascending: a strict '>' keeps the first maximum)
+#if P1K_WG4_PRIO
+        if constexpr (WG4)
+            __builtin_amdgcn_s_setprio(3);
+#endif
         wave_lds_sync();  // after the last pair's row reads of these tiles
 #if P1K_CELL_LDS && !P1K_GROUPS
         // [P][KPAD][2], 1 KiB-aligned in the wave's tiles: a gather address is
@@ -1006,6 +1109,30 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
 #pragma unroll
         for (int i = 0; i < 4; i++)
             q[i] = tups[64 * i + lane64];
+        // NW = 4: the words come from L2, so each step's are requested two
+        // steps ahead of its gathers, into the buffer the gathers of two steps
+        // before have just read
+        [[maybe_unused]] uint32_t qa[4], qb[4];
+        [[maybe_unused]] auto words = [&](uint32_t (&qq)[4], int u) {
+            const uint32_t *tl = tups + u + lane64;
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                qq[i] = tl[64 * i];
+        };
+#if P1K_WG4_TUPS_ALL
+        constexpr int TS = 14;  // steps of 256 tuples in the largest image that fits
+        [[maybe_unused]] uint32_t qall[TS][4];
+        if constexpr (WG4) {
+#pragma unroll
+            for (int s = 1; s < TS; s++)
+                words(qall[s], imin(256 * s, Upad - 256));
+        }
+#else
+        if constexpr (WG4) {
+            words(qa, 256);
+            words(qb, Upad > 512 ? 512 : 256);
+        }
+#endif
         gather(q, g);
         auto consume = [&](const f2 (&gg)[4][3], int ub) {
 #pragma unroll
@@ -1024,6 +1151,33 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
         };
         // two steps per trip (Upad is a multiple of 512): the step buffers
         // alternate instead of being copied back (24 moves a step)
+#if P1K_WG4_TUPS_ALL
+        if constexpr (WG4) {
+#pragma unroll
+            for (int s = 0; s < TS; s += 2) {
+                if (256 * s >= Upad)
+                    break;
+                f2 gn[4][3];
+                gather(qall[s + 1], gn);
+                consume(g, 256 * s);
+                gather(qall[s + 2 < TS ? s + 2 : TS - 1], g);
+                consume(gn, 256 * (s + 1));
+            }
+        } else
+#else
+        if constexpr (WG4) {
+            const int ulast = Upad - 256;  // (steps past the end re-read the last: never consumed)
+            for (int u0 = 0; u0 < Upad; u0 += 512) {
+                f2 gn[4][3];
+                gather(qa, gn);  // step u0 + 256
+                words(qa, imin(u0 + 768, ulast));
+                consume(g, u0);
+                gather(qb, g);  // step u0 + 512
+                words(qb, imin(u0 + 1024, ulast));
+                consume(gn, u0 + 256);
+            }
+        } else
+#endif
         for (int u0 = 0; u0 < Upad; u0 += 512) {
             uint32_t qn[4];
 #pragma unroll
@@ -1091,7 +1245,7 @@ __global__ void __launch_bounds__(512, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout 
             const int cells[2] = {wcell[0], wcell[1]};  // no winner (NaN scores): tuple 0
 #pragma unroll
             for (int j = 0; j < 2; j++) {
-                const int64_t fs = base + 2 * wave + j;
+                const int64_t fs = base + 2 * (WG4 ? (fresh_tid() >> 6) & (NW - 1) : wave) + j;
                 if (fs < B) {
                     if (out.cell)
                         out.cell[fs] = cells[j];
@@ -1134,11 +1288,61 @@ extern "C" int tdoa_diag_fetch_p1k(unsigned long long *host, int n)
 
 // --------------------------------------------------------------- host side
 namespace {
-constexpr int P1K_NW = 8;  // waves per workgroup (two per SIMD)
+// waves per workgroup of the product's launch (the other shape is built into
+// the A/B library only: TDOA_P1K=lean8 | lean4).  The 4-wave shape won every
+// two-stream A/B pair against the parent's kernel, by ~0.55 us of 27.3; on one
+// stream it is 12 % slower (profiles/c2_wg4_ab.txt)
+#ifndef P1K_DEFAULT_NW
+#define P1K_DEFAULT_NW 4
+#endif
 
-// dynamic LDS of a launch: the waves' tiles and the whole table image
-constexpr size_t p1k_lds(int img_bytes) { return (size_t)P1K_NW * P1K_WAVE_LDS + (size_t)img_bytes; }
+// dynamic LDS of a launch: the waves' tiles and the whole table image (8 waves)
+// or the image's prefix twm | tw2 | prior (4 waves)
+constexpr size_t p1k_lds(int nw, int img_bytes)
+{
+    return (size_t)nw * P1K_WAVE_LDS + (size_t)(nw == 4 ? P1K_IMG_LDS4 : img_bytes);
+}
+
+// the launched shape: P1K_DEFAULT_NW; in the A/B build TDOA_P1K=lean8 | lean4
+int p1k_nw()
+{
+#if TDOA_AB
+    static const int pick = [] {
+        const char *e = getenv("TDOA_P1K");
+        return e && !strcmp(e, "lean8") ? 8 : (e && !strcmp(e, "lean4") ? 4 : P1K_DEFAULT_NW);
+    }();
+    return pick;
+#else
+    return P1K_DEFAULT_NW;
+#endif
+}
+
+template <int NW>
+int p1k_launch(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames, int64_t B, float e2,
+               hipStream_t stream)
+{
+    // one workgroup of 2 NW frames (one frame per half-wave)
+    const int64_t grid = (B + 2 * NW - 1) / (2 * NW);
+    if (grid > 0x7FFFFFFF)
+        return tdoa_set_error(-1, "k_p1k_lean: batch too large for one launch");
+    hipLaunchKernelGGL(k_p1k_lean<NW>, dim3((unsigned)grid), dim3(NW * 64), p1k_lds(NW, kp.p1k_img_bytes), stream, kp,
+                       out, frames, B, e2);
+    return 0;
+}
 }  // namespace
+
+#ifdef TDOA_DIAG
+// diagnostic build only: workgroups of the launched shape resident per CU
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor with its block and LDS size)
+extern "C" int tdoa_diag_p1k_occupancy(int img_bytes, int *nw)
+{
+    int n = -1;
+    *nw = p1k_nw();
+    const hipError_t e = *nw == 4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_p1k_lean<4>, 4 * 64, p1k_lds(4, img_bytes))
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_p1k_lean<8>, 8 * 64, p1k_lds(8, img_bytes));
+    return e == hipSuccess ? n : -1;
+}
+#endif
 
 // LDS table image of k_phat1024 (layout of the kernel's shared memory from twm on)
 void tdoa_phat1024_image(int M, int N, int K, int U, const float *tw, const int32_t *win,
@@ -1209,15 +1413,15 @@ void tdoa_phat1024_image(int M, int N, int K, int U, const float *tw, const int3
             f[2 * (32 * k + slot(r)) + 1] = tw2[2 * b + 1];
         }
     f += 2 * 512;
+    for (int k = 0; k < 128; k++)
+        f[k] = k < K ? prior[k] : 0.0f;
+    f += 128;  // (the 4-wave workgroup's LDS prefix ends here: P1K_IMG_LDS4)
     for (int e = 0; e < 512; e++) {  // (W[2e], W[2e+1]) / 128, word e = 32 t + r at slot(r)
         const int d = (e & ~31) + slot(e & 31);
         f[2 * d] = (float)win[2 * e] * (1.0f / 128.0f);
         f[2 * d + 1] = (float)win[2 * e + 1] * (1.0f / 128.0f);
     }
-    f += 2 * 512;
-    for (int k = 0; k < 128; k++)
-        f[k] = k < K ? prior[k] : 0.0f;
-    uint32_t *t = (uint32_t *)(f + 128);
+    uint32_t *t = (uint32_t *)(f + 2 * 512);
 #if P1K_GROUPS
     // header: slots per bucket (n = 3, 2, 1), tuple 0's cell; then the group
     // words (LDS byte offsets of l0, l1 and the first l2 in a wave's [p][KPAD]
@@ -1278,7 +1482,9 @@ bool tdoa_phat1024_fits(const tdoa_kparams &kp)
     // grid scores of a wave's two frames live in its tiles: [3][KPAD] float2 = 3 KiB
     static_assert(3 * P1K_KPAD * 8 <= P1K_WAVE_LDS, "grid scores exceed the wave's tiles");
     // the image loads as at most 4 units of 16 B per thread (k_p1k_lean's staging)
-    return kp.p1k_img_bytes <= 4 * P1K_NW * 64 * 16 && p1k_lds(kp.p1k_img_bytes) + 64 <= 160 * 1024;  // + the static progress words
+    // and, with 8 waves' tiles and the static progress words, fits the CU's LDS.
+    // The 4-wave shape stages a fixed prefix only, so the same contexts fit it
+    return kp.p1k_img_bytes <= 4 * 8 * 64 * 16 && p1k_lds(8, kp.p1k_img_bytes) + 64 <= 160 * 1024;
 }
 
 int tdoa_launch_phat1024(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames,
@@ -1291,13 +1497,15 @@ int tdoa_launch_phat1024(const tdoa_kparams &kp, const tdoa_kout &out, const int
         e2 = 1e-30f;
     if (B <= 0)
         return 0;
-    // one workgroup of 16 frames (8 waves, one frame per half-wave) per group
-    constexpr int NF = 2 * P1K_NW;
-    const int64_t grid = (B + NF - 1) / NF;
-    if (grid > 0x7FFFFFFF)
-        return tdoa_set_error(-1, "k_p1k_lean: batch too large for one launch");
-    hipLaunchKernelGGL(k_p1k_lean, dim3((unsigned)grid), dim3(P1K_NW * 64), p1k_lds(kp.p1k_img_bytes), (hipStream_t)stream,
-                       kp, out, frames, B, e2);
+    int rc;
+#if TDOA_AB
+    rc = p1k_nw() == 4 ? p1k_launch<4>(kp, out, frames, B, e2, (hipStream_t)stream)
+                       : p1k_launch<8>(kp, out, frames, B, e2, (hipStream_t)stream);
+#else
+    rc = p1k_launch<P1K_DEFAULT_NW>(kp, out, frames, B, e2, (hipStream_t)stream);
+#endif
+    if (rc)
+        return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         char buf[256];

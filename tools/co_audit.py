@@ -166,6 +166,8 @@ def audit(so_path: str) -> dict[str, dict]:
                     "vgpr_spill": int(md.get(".vgpr_spill_count", 0)),
                     "sgpr_spill": int(md.get(".sgpr_spill_count", 0)),
                     "vgprs": int(md.get(".vgpr_count", 0)),
+                    "agprs": int(md.get(".agpr_count", 0)),
+                    "lds_static": int(md.get(".group_segment_fixed_size", 0)),
                     "instructions": len(insts),
                     "calls": sum(1 for s in insts if s.startswith(("s_swappc", "s_setpc", "s_call"))),
                     "flat": sum(1 for s in insts if s.startswith("flat_")),
@@ -184,7 +186,7 @@ def main():
         flag = "" if not (r["private_segment"] or r["calls"] or r["flat"] or r["trans_use"] or r["smem_split"]) \
             else "  <--"
         print(f"{name[:90]:90s} priv {r['private_segment']:4d} spill {r['vgpr_spill']:2d}/{r['sgpr_spill']:3d} "
-              f"vgpr {r['vgprs']:3d} calls {r['calls']} flat {r['flat']:3d} trans-use {len(r['trans_use'])} "
+              f"vgpr {r['vgprs']:3d} agpr {r['agprs']:3d} calls {r['calls']} flat {r['flat']:3d} trans-use {len(r['trans_use'])} "
               f"smem-split {len(r['smem_split'])}{flag}")
         for v in (r["trans_use"] + r["smem_split"])[:4]:
             print("    ", v)

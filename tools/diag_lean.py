@@ -3,6 +3,12 @@
 at its phase boundaries).  Diagnostic only; never used by tests or bench.py.
 
     python tools/diag_lean.py [B]
+
+The diag library holds both workgroup shapes (TDOA_P1K=lean8 | lean4, default:
+the product's).  Also prints the runtime's occupancy answer for the launched
+shape (workgroups per CU) and, from the realtime stamps, how far apart the
+workgroups of one launch start: all resident at once means all within about a
+microsecond.
 """
 import ctypes as C
 import os
@@ -34,6 +40,11 @@ L = tdoa.load()
 L.tdoa_diag_fetch_p1k.argtypes = [C.c_void_p, C.c_int]
 buf = np.zeros(1 << 16, np.uint64)
 assert L.tdoa_diag_fetch_p1k(buf.ctypes.data_as(C.c_void_p), 1 << 16) == 0
+L.tdoa_diag_p1k_occupancy.argtypes = [C.c_int, C.POINTER(C.c_int)]
+nw = C.c_int(0)
+occ = L.tdoa_diag_p1k_occupancy(16896 + 2560 * 4, C.byref(nw))  # (8 waves stage the whole image: config 2's size)
+NW = nw.value
+print(f"k_p1k_lean<{NW}>: hipOccupancyMaxActiveBlocksPerMultiprocessor = {occ} workgroups per CU")
 st = buf.reshape(-1, 16).astype(np.int64)
 st = st[st[:, 0] > 0]
 names = ["start", "staged", "mic0", "mic1", "pair01", "mic2+cross", "pair02", "pair12",
@@ -57,12 +68,16 @@ for i in range(1, n):
     print(f"  {names[i]:11s} {np.percentile(d, 10):8.0f} {np.median(d):8.0f} {np.percentile(d, 90):8.0f}")
 life = (st[:, 15] - st[:, 14]) / 100.0  # us
 end = (st[:, 15] - st[:, 14].min()) / 100.0
-blk = np.nonzero(buf.reshape(-1, 16)[:, 0] > 0)[0]  # global wave index = block * 8 + wave
-wv = blk % 8
-xcd = (blk // 8) % 8
+blk = np.nonzero(buf.reshape(-1, 16)[:, 0] > 0)[0]  # global wave index = block * NW + wave
+wv = blk % NW
+xcd = (blk // NW) % 8
+wg = blk // NW
+wg_start = np.array([rt[wg == g].min() for g in np.unique(wg)]) / 100.0
+print(f"workgroups {len(wg_start)}: first-wave start (us) p50 {np.median(wg_start):.2f} p99 "
+      f"{np.percentile(wg_start, 99):.2f} max {wg_start.max():.2f}")
 print("wave life (us): p10 %.2f p50 %.2f p90 %.2f p99 %.2f max %.2f" % tuple(np.percentile(life, [10, 50, 90, 99, 100])))
 print("wave end  (us): p10 %.2f p50 %.2f p90 %.2f p99 %.2f max %.2f" % tuple(np.percentile(end, [10, 50, 90, 99, 100])))
-print("end by wave-in-workgroup:", " ".join(f"{np.median(end[wv == w]):.1f}" for w in range(8)))
+print("end by wave-in-workgroup:", " ".join(f"{np.median(end[wv == w]):.1f}" for w in range(NW)))
 print("end by block % 8 (XCD):  ", " ".join(f"{np.median(end[xcd == x]):.1f}" for x in range(8)))
 m0 = t[:, 2] - t[:, 1]
-print("mic0 phase by wave-in-workgroup (kcyc):", " ".join(f"{np.median(m0[wv == w]) / 1e3:.1f}" for w in range(8)))
+print("mic0 phase by wave-in-workgroup (kcyc):", " ".join(f"{np.median(m0[wv == w]) / 1e3:.1f}" for w in range(NW)))

@@ -45,6 +45,7 @@
 
 #include "tdoa_cplx.h"
 #include "tdoa_internal.h"
+#include "tdoa_tables.h"  // the pruned scan's row table (tdoa_p1k_prune_section)
 
 // TDOA_AB=1: the A/B build (tdoa/libtdoa_ab.so) holds both workgroup shapes of
 // k_p1k_lean; the product holds the one it launches
@@ -63,6 +64,10 @@ constexpr int P1K_WAVE_LDS = 2 * P1K_TILE;  // a wave's two transpose tiles (one
 // The first P1K_IMG_LDS4 bytes are all that the 4-wave workgroup keeps in LDS.
 constexpr int P1K_IMG_LDS4 = 32 * 32 * 8 + 16 * 32 * 8 + 128 * 4;
 constexpr int P1K_IMG_FIXED = P1K_IMG_LDS4 + 512 * 8;
+// tuple words of the exhaustive scan: U padded to whole double steps of 256.
+// With P1K_GRID_PRUNE the pruned scan's row table follows them in the image
+// (global memory only: no workgroup stages it)
+__host__ __device__ constexpr int p1k_upad(int U) { return (U + P1K_GB * 64 - 1) / (P1K_GB * 64) * (P1K_GB * 64); }
 
 // Tile row / column and table column of residue (or DFT index) x: 16 and 24
 // swap places, so the residues of every 16-lane group of a half-wave --
@@ -224,6 +229,24 @@ __device__ __forceinline__ f2 lds_f2(const char *base, int off)
 #ifndef P1K_WG4_TUPS_ALL
 #define P1K_WG4_TUPS_ALL 0
 #endif
+// P1K_GRID_PRUNE=1: the 4-wave workgroup scans only the rows of 64 tuples whose
+// exact upper bound is not below the best L found so far (see the grid solve;
+// the table image carries the rows after the tuple words).  0: the exhaustive
+// scan of every tuple, as the 8-wave workgroup's always is; same outputs.
+// Not with the scan variants that lay the image's tail out differently
+#ifndef P1K_GRID_PRUNE
+#define P1K_GRID_PRUNE 1
+#endif
+#if P1K_GROUPS || P1K_CELL_LDS
+#undef P1K_GRID_PRUNE
+#define P1K_GRID_PRUNE 0
+#endif
+// the image's bytes up to the pruned scan's row table: what the 8-wave
+// workgroup keeps in LDS
+__host__ __device__ inline int p1k_img_lds8(const tdoa_kparams &kp)
+{
+    return P1K_GRID_PRUNE ? P1K_IMG_FIXED + 4 * p1k_upad(kp.U) : kp.p1k_img_bytes;
+}
 // plain LDS read (the grid's gathers: data-dependent addresses, never merged,
 // and free to be scheduled around the other reads of the software pipeline)
 __device__ __forceinline__ f2 lds_f2_plain(const char *base, int off)
@@ -551,7 +574,10 @@ __device__ __forceinline__ void lean_pretwiddle(const Lane &L, const f2 (&A)[33]
 //           the tiles and the image's prefix twm | tw2 | prior; the window
 //           comes from kp.window with the row's words and the grid's tuple
 //           words from the image in global memory (L2), two steps ahead.
-// The per-frame arithmetic and its order are the same, so are all outputs.
+//           Its grid solve scans only the rows of tuples whose upper bound
+//           reaches the best L (P1K_GRID_PRUNE); NW = 8 scans every tuple.
+// The per-frame arithmetic and its order are the same, and the pruned scan
+// is exact, so all outputs are the same bytes.
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_kout out,
                                                          const int16_t *__restrict__ frames, int64_t B,
@@ -560,6 +586,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
     static_assert(NW == 4 || NW == 8, "k_p1k_lean: 4 or 8 waves per workgroup");
     constexpr int N = 1024, P = 3, NF = 2 * NW, NT = NW * 64;
     constexpr bool WG4 = NW == 4;
+    constexpr bool PRUNE = WG4 && P1K_GRID_PRUNE;
     static_assert(!WG4 || NW * P1K_WAVE_LDS + P1K_IMG_LDS4 <= 80 * 1024, "two workgroups must fit a CU's 160 KiB of LDS");
     static_assert(!WG4 || !P1K_GROUPS, "the grouped scan reads its words from LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -642,7 +669,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
     const int K = kp.K, S = kp.S;
     const bool do_grid = out.cell || out.xy || out.max_Lf;
 #if !P1K_GROUPS
-    const int Upad = (kp.U + P1K_GB * 64 - 1) / (P1K_GB * 64) * (P1K_GB * 64);
+    const int Upad = p1k_upad(kp.U);
 #endif
 
     constexpr int NQ = WG4 ? 16 : 1;  // (NW = 8: one unused word)
@@ -671,7 +698,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
     {
         const uint4 *src = (const uint4 *)kp.p1k_img;
         uint4 *dst = (uint4 *)twm;
-        const int n16 = WG4 ? P1K_IMG_LDS4 / 16 : (do_grid ? kp.p1k_img_bytes / 16 : P1K_IMG_FIXED / 16);
+        const int n16 = WG4 ? P1K_IMG_LDS4 / 16 : (do_grid ? p1k_img_lds8(kp) / 16 : P1K_IMG_FIXED / 16);
         constexpr int SR = 4;  // image <= SR * NT * 16 B = 32 KiB (tdoa_phat1024_fits)
         uint4 img[SR];
 #pragma unroll
@@ -712,6 +739,9 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
         LEAN_MARK();
         float wv[3][4];
         int best[3];
+        // the pruned scan's per-pair term: an upper bound of the pair's weighted
+        // scores, per frame of the wave (uniform values: scalar registers)
+        [[maybe_unused]] float pm[3][2] = {};
         auto finish_pair = [&](int p, f2 y0, f2 y31) {
             // this lane's four candidate lags (recomputed here, see fresh_tid)
             const int ft = fresh_tid();
@@ -732,6 +762,21 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
                 }
             }
             half_argmax_key(bkey, bk);  // every lane of the half-wave
+            if constexpr (PRUNE) {
+                // M = max(raw maximum, 0) >= every weighted score of the pair, in
+                // float, without another reduction: a weighted score is
+                // fl(c * s) with c the raw score and 0 <= s <= 1 a prior value
+                // (exp of a non-positive float; s = 1 exactly at distance 0).
+                // c >= 0: c * s <= c, and rounding is monotone with c itself
+                // representable, so fl(c * s) <= c <= raw maximum.  c < 0:
+                // c * s <= 0, so fl(c * s) <= 0.  Where the raw maximum is >= 0
+                // it is its own weighted score (s = 1 at the best lag) and M is
+                // the exact maximum; where every score is negative, weighting
+                // moves scores toward zero and only 0 bounds them.
+                const int mb = __builtin_bit_cast(int, fmaxf(fkey_value(bkey), 0.0f));
+                pm[p][0] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(mb, 0));
+                pm[p][1] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(mb, 32));
+            }
             bk = bk < 0 ? 0 : (bk >= K ? K - 1 : bk);
             best[p] = bk - S;
             const int64_t ff = base + 2 * ((ft >> 6) & (NW - 1)) + fhw;
@@ -861,6 +906,22 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
             __builtin_amdgcn_s_setprio(3);
 #endif
         wave_lds_sync();  // after the last pair's row reads of these tiles
+        // the pruned scan's row table (after the tuple words in the global
+        // image): its header and this lane's row record, requested here so the
+        // L2 round trip passes under the score writes below
+#if P1K_GRID_PRUNE
+        [[maybe_unused]] const uint32_t *ps = nullptr;
+        [[maybe_unused]] uint32_t prows = 0, ppair = 0, pwid = 0, prec = 0;
+        [[maybe_unused]] int pcell0 = 0;
+        if constexpr (PRUNE) {
+            ps = tups + Upad;
+            prows = ps[0];
+            ppair = ps[1];
+            pwid = ps[2];
+            pcell0 = (int)ps[3];
+            prec = ps[TDOA_P1K_PRUNE_HDR + lane64];
+        }
+#endif
 #if P1K_CELL_LDS && !P1K_GROUPS
         // [P][KPAD][2], 1 KiB-aligned in the wave's tiles: a gather address is
         // then one and-or of a tuple field with the table base
@@ -885,6 +946,158 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
         }
         wave_lds_sync();  // the gathers read other lanes' score slots
         LEAN_MARK();
+        float gv[2] = {-INFINITY, -INFINITY};
+        int wcell[2];
+        // the exhaustive scan runs: always without the pruned scan, and with it
+        // where the row bounds prune too little to pay for themselves (below)
+        bool full = !PRUNE;
+#if P1K_GRID_PRUNE
+        if constexpr (PRUNE) {
+            // Pruned scan, exact.  The image holds the tuples sorted by the lag
+            // of one pair p (ties in first-cell order) in rows of 64, one tuple
+            // per lane, each with its first cell, and per row the range
+            // [lo, hi] of pair p's lag slots.  For a frame, with w_q the
+            // weighted scores of pair q and M_q >= max w_q (finish_pair),
+            //   bound(row) = (t0 + t1) + t2,  t_p = max w_p[lo..hi],  t_q = M_q,
+            // summed in L's own order and association.  Every tuple of the row
+            // has w_q[l_q] <= t_q, and a rounded float sum never decreases when
+            // a term grows, so bound >= the float L of each of its tuples: a row
+            // with bound < (an L already found) holds neither the maximum nor a
+            // tie with it.  Only a true '<' skips a row, so a NaN on either side
+            // skips nothing (v_max drops a NaN score: its tuples' L is NaN and
+            // never wins).  The lag prior makes w_p a narrow bump, so few rows
+            // pass (~4 of 39 on ADC frames; all of them on uncorrelated noise).
+            // Order: lane r bounds row r for both frames.  Pass 1 scans the rows
+            // that have either frame's largest bound (the rows whose range holds
+            // pair p's best lag: one to three a frame, and on ADC frames the
+            // maximum is nearly always among them); pass 2 the rows whose bound
+            // is not below either frame's best of pass 1 (usually none).  A pass
+            // scans its rows four at a time, each batch's words and cells
+            // requested (clamped, unguarded, no store before them) ahead of the
+            // previous batch's gathers.  Sorted order is not first-cell order,
+            // so every compare carries the cell: larger L, or equal L and a
+            // smaller cell.
+            // Flat scores (uncorrelated microphones) leave most rows to pass 2,
+            // whose rows cost about twice the exhaustive scan's per tuple (the
+            // cell words and compares): when pass 2 would scan more than half of
+            // the rows, the exhaustive scan below runs instead and pass 1 is
+            // dropped (4096 noise frames: 1.6 us per launch slower than the
+            // exhaustive kernel without this, DESIGN.md has the figures with it).
+            const char *ws = (const char *)wsc;
+            const int lo = (int)(prec & 0xFFu), hi = (int)((prec >> 8) & 0xFFu);
+            const char *wsp = ws + (int)ppair * (P1K_KPAD * 8);
+            f2 wm = f2{-INFINITY, -INFINITY};
+#pragma nounroll
+            for (int j0 = 0; j0 < (int)pwid; j0 += 4) {  // (one trip: rows span <= 4 lags in config 2)
+                f2 v[4];
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    v[j] = lds_f2_plain(wsp, 8 * imin(lo + j0 + j, hi));
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    wm = f2{fmaxf(wm.x, v[j].x), fmaxf(wm.y, v[j].y)};
+            }
+            const f2 t0 = ppair == 0 ? wm : f2{pm[0][0], pm[0][1]};
+            const f2 t1 = ppair == 1 ? wm : f2{pm[1][0], pm[1][1]};
+            const f2 t2 = ppair == 2 ? wm : f2{pm[2][0], pm[2][1]};
+            const f2 bnd = (t0 + t1) + t2;
+            const bool rowok = (uint32_t)lane64 < prows;
+            const uint64_t allrows = __ballot(rowok);
+            uint64_t mask = 0;
+#pragma unroll
+            for (int f = 0; f < 2; f++) {  // the rows that have the frame's largest bound
+                const int k = rowok ? fkey(f ? bnd.y : bnd.x) : INT_MIN;
+                mask |= __ballot(k == wave_reduce<true>(k));
+            }
+            mask &= allrows;
+            // row R's words and cells: a uniform base plus the lane
+            const uint32_t *ptw = ps + TDOA_P1K_PRUNE_HDR + 64;
+            const int32_t *pcl = (const int32_t *)(ptw + 64 * prows);
+            float bv[2] = {-INFINITY, -INFINITY};
+            int bc[2] = {INT_MAX, INT_MAX}, vk[2] = {fkey(-INFINITY), fkey(-INFINITY)};
+            constexpr int RB = 4;
+            auto rowscan = [&](const uint32_t(&w)[RB], const int(&c)[RB]) {
+                f2 g[RB][3];
+#pragma unroll
+                for (int i = 0; i < RB; i++) {
+                    g[i][0] = lds_f2_plain(ws, (int)(w[i] & 0x3FFu));
+                    g[i][1] = lds_f2_plain(ws, P1K_KPAD * 8 + (int)((w[i] >> 10) & 0x3FFu));
+                    g[i][2] = lds_f2_plain(ws, 2 * P1K_KPAD * 8 + (int)(w[i] >> 20));
+                }
+#pragma unroll
+                for (int i = 0; i < RB; i++) {
+                    const f2 Lg = (g[i][0] + g[i][1]) + g[i][2];
+#pragma unroll
+                    for (int f = 0; f < 2; f++) {
+                        const float l = f ? Lg.y : Lg.x;
+                        const bool take = (l > bv[f]) | ((l == bv[f]) & (c[i] < bc[f]));  // (no branches)
+                        bv[f] = take ? l : bv[f];
+                        bc[f] = take ? c[i] : bc[f];
+                    }
+                }
+            };
+            int R = 0;
+            // the next RB rows of the mask; once it is empty, the last row again
+            // (scanning a row twice changes nothing: no larger L, no smaller cell)
+            auto request = [&](uint32_t(&w)[RB], int(&c)[RB]) {
+#pragma unroll
+                for (int i = 0; i < RB; i++) {
+                    if (mask) {
+                        R = (int)__builtin_ctzll(mask);
+                        mask &= mask - 1;
+                    }
+                    w[i] = (ptw + 64 * R)[lane64];
+                    c[i] = (pcl + 64 * R)[lane64];
+                }
+                // the loads stay here: without this the compiler sinks a batch's
+                // loads below the branch that ends the pass, behind the previous
+                // batch's scan, and each batch is an L2 round trip of its own
+                asm volatile("" ::: "memory");
+            };
+            uint64_t done = 0;
+            for (int pass = 0; pass < 2 && mask && !full; pass++) {
+                done |= mask;
+                // two register sets, no copies (a copy would wait for its loads)
+                uint32_t wa[RB], wb[RB];
+                int ca[RB], cb[RB];
+                request(wa, ca);
+                for (;;) {
+                    const bool more_b = mask != 0;
+                    request(wb, cb);
+                    rowscan(wa, ca);
+                    if (!more_b)
+                        break;
+                    const bool more_a = mask != 0;
+                    request(wa, ca);
+                    rowscan(wb, cb);
+                    if (!more_a)
+                        break;
+                }
+                // the wave's best so far, and after pass 1 the rows that can
+                // still hold a larger L or a tie of either frame
+#pragma unroll
+                for (int f = 0; f < 2; f++)
+                    vk[f] = wave_reduce<true>(fkey(bv[f]));
+                if (pass == 0) {
+                    mask = __ballot(!(bnd.x < fkey_value(vk[0])) || !(bnd.y < fkey_value(vk[1]))) & allrows & ~done;
+                    full = 2 * __builtin_popcountll(mask) > (int)prows;
+                }
+            }
+            if (!full) {
+                LEAN_MARK();
+                // (max L, smallest first cell) over the wave; no L above -inf
+                // (NaN scores): tuple 0, as the exhaustive scan answers
+#pragma unroll
+                for (int j = 0; j < 2; j++) {
+                    const int ci = wave_reduce<false>(fkey(bv[j]) == vk[j] ? bc[j] : INT_MAX);
+                    gv[j] = fkey_value(vk[j]);
+                    wcell[j] = gv[j] > -INFINITY ? ci : pcell0;
+                }
+                LEAN_MARK();
+            }
+        }
+#endif
+        if (full) {
 #if P1K_GROUPS
         // Tuples grouped by their first two lags (tdoa_phat1024_image): a
         // group word holds the LDS offsets of lags l0, l1 and the first of n
@@ -908,7 +1121,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
         // per frame: the largest group maximum, the first slot that reached it
         // (strict '>') and the last slot that matched it ('>='); they differ
         // exactly when a later group tied the maximum
-        float gv[2] = {-INFINITY, -INFINITY};
         int gs[2] = {0, 0}, gsl[2] = {0, 0};
         const char *ws = (const char *)wsc;
         constexpr int R1 = P1K_KPAD * 8, R2 = 2 * P1K_KPAD * 8;
@@ -1053,7 +1265,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
                 cand[f] = gv[f] > -INFINITY ? mc : INT_MAX;
             }
         }
-        int wcell[2];
 #pragma unroll
         for (int j = 0; j < 2; j++) {
             int ci = cand[j];
@@ -1073,7 +1284,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
         }
         LEAN_MARK();
 #else
-        float gv[2] = {-INFINITY, -INFINITY};
         int gu[2] = {INT_MAX, INT_MAX};
         const char *ws = (const char *)wsc;
         // lane-strided: the 32 lanes of a gather read 32 consecutive tuples
@@ -1228,7 +1438,6 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
             gv[j] = fkey_value(gk[j]);
         }
         LEAN_MARK();
-        int wcell[2];
 #if P1K_CELL_LDS
         const int tuple_cell0 = rowcell[0];  // (offset 0)
 #else
@@ -1241,6 +1450,7 @@ __global__ void __launch_bounds__(NW * 64, 2) k_p1k_lean(tdoa_kparams kp, tdoa_k
             wcell[j] = wm ? __builtin_amdgcn_readlane(mycell[j], __builtin_ctzll(wm)) : tuple_cell0;
         }
 #endif
+        }
         if (lane64 == 63) {
             const int cells[2] = {wcell[0], wcell[1]};  // no winner (NaN scores): tuple 0
 #pragma unroll
@@ -1291,7 +1501,9 @@ namespace {
 // waves per workgroup of the product's launch (the other shape is built into
 // the A/B library only: TDOA_P1K=lean8 | lean4).  The 4-wave shape won every
 // two-stream A/B pair against the parent's kernel, by ~0.55 us of 27.3; on one
-// stream it is 12 % slower (profiles/c2_wg4_ab.txt)
+// stream it is 12 % slower (profiles/c2_wg4_ab.txt).  Only the
+// 4-wave shape prunes its grid scan (P1K_GRID_PRUNE: 1.46 us of 26.7 on two
+// streams, profiles/c2_grid_prune_ab.txt); lean8 is the exhaustive scan's A/B build
 #ifndef P1K_DEFAULT_NW
 #define P1K_DEFAULT_NW 4
 #endif
@@ -1325,7 +1537,7 @@ int p1k_launch(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *fram
     const int64_t grid = (B + 2 * NW - 1) / (2 * NW);
     if (grid > 0x7FFFFFFF)
         return tdoa_set_error(-1, "k_p1k_lean: batch too large for one launch");
-    hipLaunchKernelGGL(k_p1k_lean<NW>, dim3((unsigned)grid), dim3(NW * 64), p1k_lds(NW, kp.p1k_img_bytes), stream, kp,
+    hipLaunchKernelGGL(k_p1k_lean<NW>, dim3((unsigned)grid), dim3(NW * 64), p1k_lds(NW, p1k_img_lds8(kp)), stream, kp,
                        out, frames, B, e2);
     return 0;
 }
@@ -1389,7 +1601,7 @@ void tdoa_phat1024_image(int M, int N, int K, int U, const float *tw, const int3
     const size_t bytes = (size_t)P1K_IMG_FIXED + 16 + 4 * (size_t)(nslot[3] + nslot[2] + nslot[1]) + 2 * (size_t)ncell;
     img.resize((bytes + 15) / 16 * 16);
 #else
-    const int Upad = (U + P1K_GB * 64 - 1) / (P1K_GB * 64) * (P1K_GB * 64);
+    const int Upad = p1k_upad(U);
 #if P1K_CELL_LDS
     img.resize((size_t)P1K_IMG_FIXED + (size_t)Upad * 4 + (size_t)(Upad / 32) * 4);  // + the row cells
 #else
@@ -1470,6 +1682,20 @@ void tdoa_phat1024_image(int M, int N, int K, int U, const float *tw, const int3
         const uint32_t wd = e < U ? tuples[e] : 0x007F7F7Fu;
         t[e] = ((wd & 0xFFu) << 3) | (((wd >> 8) & 0xFFu) << 13) | (((wd >> 16) & 0xFFu) << 23);
     }
+#if P1K_GRID_PRUNE
+    // the pruned scan's row table, appended (16-B aligned: Upad is a multiple
+    // of 512); a table of more than 64 rows has no image: the generic kernel
+    // runs it, as it does every table the 8-wave workgroup cannot stage
+    std::vector<uint32_t> sec;
+    tdoa_p1k_prune_section(U, tuples, tuple_cell, sec);
+    if (sec.empty()) {
+        img.clear();
+        return;
+    }
+    sec.resize((sec.size() + 3) / 4 * 4);
+    const uint8_t *sb = (const uint8_t *)sec.data();
+    img.insert(img.end(), sb, sb + sec.size() * 4);
+#endif
 #endif
 #endif
 }
@@ -1483,8 +1709,11 @@ bool tdoa_phat1024_fits(const tdoa_kparams &kp)
     static_assert(3 * P1K_KPAD * 8 <= P1K_WAVE_LDS, "grid scores exceed the wave's tiles");
     // the image loads as at most 4 units of 16 B per thread (k_p1k_lean's staging)
     // and, with 8 waves' tiles and the static progress words, fits the CU's LDS.
-    // The 4-wave shape stages a fixed prefix only, so the same contexts fit it
-    return kp.p1k_img_bytes <= 4 * 8 * 64 * 16 && p1k_lds(8, kp.p1k_img_bytes) + 64 <= 160 * 1024;
+    // The 4-wave shape stages a fixed prefix only, so the same contexts fit it.
+    // (The pruned scan's row table after the staged bytes stays in global
+    // memory; a staged part within 32 KiB has at most 56 rows of 64 tuples.)
+    const int lds8 = p1k_img_lds8(kp);
+    return lds8 <= kp.p1k_img_bytes && lds8 <= 4 * 8 * 64 * 16 && p1k_lds(8, lds8) + 64 <= 160 * 1024;
 }
 
 int tdoa_launch_phat1024(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *frames,

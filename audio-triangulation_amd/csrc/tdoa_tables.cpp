@@ -571,6 +571,57 @@ void build_kparams(tdoa_tables *c)
 
 }  // namespace
 
+// The pruned grid scan's row table (tdoa_tables.h has the layout): for each
+// pair the tuples stably sorted by that pair's lag slot and cut into rows of
+// 64; the sort pair is the one whose widest row spans the fewest lags (then
+// the smallest sum of widths, then the lowest pair).
+void tdoa_p1k_prune_section(int U, const uint32_t *tuples, const int32_t *tuple_cell, std::vector<uint32_t> &sec)
+{
+    sec.clear();
+    const int rows = (U + 63) / 64;
+    if (U <= 0 || rows > 64)
+        return;
+    std::vector<int> order[3];
+    int wmax[3], wsum[3], best = 0;
+    for (int p = 0; p < 3; p++) {
+        order[p].resize(U);
+        for (int u = 0; u < U; u++)
+            order[p][u] = u;
+        std::stable_sort(order[p].begin(), order[p].end(), [&](int a, int b) {
+            return ((tuples[a] >> (8 * p)) & 0xFFu) < ((tuples[b] >> (8 * p)) & 0xFFu);
+        });
+        wmax[p] = wsum[p] = 0;
+        for (int r = 0; r < rows; r++) {
+            const int lo = (tuples[order[p][64 * r]] >> (8 * p)) & 0xFF;
+            const int hi = (tuples[order[p][std::min(U, 64 * r + 64) - 1]] >> (8 * p)) & 0xFF;
+            wmax[p] = std::max(wmax[p], hi - lo + 1);
+            wsum[p] += hi - lo + 1;
+        }
+        if (wmax[p] < wmax[best] || (wmax[p] == wmax[best] && wsum[p] < wsum[best]))
+            best = p;
+    }
+    const std::vector<int> &o = order[best];
+    sec.resize(TDOA_P1K_PRUNE_HDR + 64 + 2 * (size_t)rows * 64);
+    sec[0] = (uint32_t)rows;
+    sec[1] = (uint32_t)best;
+    sec[2] = (uint32_t)wmax[best];
+    sec[3] = (uint32_t)tuple_cell[0];
+    uint32_t *rec = sec.data() + TDOA_P1K_PRUNE_HDR, *wd = rec + 64, *cl = wd + (size_t)rows * 64;
+    for (int r = 0; r < 64; r++) {
+        // (records past the last row: the padding slot 127, whose score is -inf)
+        const uint32_t lo = r < rows ? (tuples[o[64 * r]] >> (8 * best)) & 0xFFu : 127u;
+        const uint32_t hi = r < rows ? (tuples[o[std::min(U, 64 * r + 64) - 1]] >> (8 * best)) & 0xFFu : 127u;
+        rec[r] = lo | (hi << 8);
+    }
+    for (int e = 0; e < rows * 64; e++) {
+        // the word as in the exhaustive scan's table: LDS byte offsets of the f2
+        // slots, 10 bits a pair; the padding tuple (127, 127, 127) scores -inf
+        const uint32_t t = e < U ? tuples[o[e]] : 0x007F7F7Fu;
+        wd[e] = ((t & 0xFFu) << 3) | (((t >> 8) & 0xFFu) << 13) | (((t >> 16) & 0xFFu) << 23);
+        cl[e] = e < U ? (uint32_t)tuple_cell[o[e]] : 0x7FFFFFFFu;
+    }
+}
+
 int tdoa_build_tables(const tdoa_config *cfg, tdoa_tables *c)
 {
     const int M = cfg->num_mics, N = cfg->frame_len;

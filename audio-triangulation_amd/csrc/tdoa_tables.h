@@ -49,3 +49,15 @@ struct tdoa_tables {
 // Validate cfg and fill *t.  TDOA_OK, or the TDOA_ERR_* code with the message
 // left for tdoa_last_error.
 int tdoa_build_tables(const tdoa_config *cfg, tdoa_tables *t);
+
+// The pruned grid scan of k_p1k_lean (tdoa_phat1024.hip, three pairs, one
+// tuple word per tuple): the distinct tuples sorted by the lag slot of one
+// pair -- ties in first-cell order -- and cut into rows of 64, as 32-bit words:
+//   [0] rows  [1] the sort pair  [2] the widest row's span in lags  [3] tuple 0's first cell
+//   [4 .. 68)       per row lo | hi << 8: the sort pair's lag slots its tuples use
+//   [68 .. + 64 rows) the tuples as LDS byte offsets (slot << 3 in bits 0-9, 10-19, 20-29)
+//   [.. + 64 rows)    their first cells
+// The last row is padded with the tuple (127, 127, 127), cell INT_MAX.  Empty
+// when the tuples make more than 64 rows.
+#define TDOA_P1K_PRUNE_HDR 4
+void tdoa_p1k_prune_section(int U, const uint32_t *tuples, const int32_t *tuple_cell, std::vector<uint32_t> &sec);

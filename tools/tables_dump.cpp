@@ -9,7 +9,7 @@
 // grid_scale, height_offset, phat_eps (one float); mic_xy (2 M floats) and
 // window_q15 (N integers) optional.
 // OUTDIR gets one raw file per table (win, prior, mic, lut, tuples, tuple_cell,
-// tw, bb_img, wc_lo, wc_w, wc_off, wc_chunks, fg); stdout one JSON object of
+// tw, bb_img, wc_lo, wc_w, wc_off, wc_chunks, fg, p1k_prune); stdout one JSON object of
 // the scalars.  Exit 0, or 1 with {"error": code, "message": ...} on stdout
 // when the config is rejected (2: the tool's own usage / IO errors).
 #include <cinttypes>
@@ -155,6 +155,11 @@ int main(int argc, char **argv)
     const int fg_ok = 0;
     const size_t fg_tup_at = 0;
 #endif
+    // k_p1k_lean's pruned-scan row table (three pairs in one tuple word; else empty)
+    std::vector<uint32_t> prune;
+    if (t.P == 3 && t.TW == 1)
+        tdoa_p1k_prune_section(t.U, t.tuples.data(), t.tuple_cell.data(), prune);
+    ok = ok && put_vec(dir, "p1k_prune", prune);
     if (!ok) {
         fprintf(stderr, "tables_dump: cannot write under %s\n", argv[2]);
         return 2;

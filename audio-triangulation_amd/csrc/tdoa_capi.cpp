@@ -501,6 +501,7 @@ const tdoa_kparams *tdoa_ctx_kparams(const tdoa_ctx *c) { return &c->kp; }
 int tdoa_ctx_device(const tdoa_ctx *c) { return c->device; }
 int tdoa_ctx_engine(const tdoa_ctx *c) { return c->t.cfg.engine; }
 int tdoa_ctx_rate(const tdoa_ctx *c) { return c->t.cfg.sample_rate_hz; }
+float tdoa_ctx_phat_eps(const tdoa_ctx *c) { return c->t.cfg.phat_eps; }
 
 extern "C" int tdoa_localize_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B,
                                    const tdoa_outputs *out, void *stream)

@@ -166,6 +166,17 @@ size_t tdoa_stream_trigger_lds(int M, int N, int H);
 int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *stream, bool *by_id);
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,
                               const tdoa_stream_kout &out, int64_t S, void *stream);
+// the GCC_PHAT hop after the trigger (tdoa_stream_phat.hip, k_stream_phat):
+// its dynamic LDS, whether the shape fits, the launch size for S streams
+// (resident workgroups, capped by `cap` > 0), and the launch -- est is the
+// float EMA state [S][P][K] (sp.est, sp.fresh* are not read), by_id as
+// tdoa_launch_stream_trigger answered
+size_t tdoa_stream_phat_lds(const tdoa_kparams &kp);
+bool tdoa_stream_phat_fits(const tdoa_kparams &kp);
+int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap);
+int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
+                            float *est, float *max_Lf, int64_t S, bool by_id, float phat_eps, int grid,
+                            void *stream);
 int tdoa_launch_average(const tdoa_kparams &kp, int64_t S, int64_t *est,
                         const int64_t *fresh, const float *decay, int32_t *best,
                         const tdoa_kout *solve, void *stream);
@@ -228,3 +239,4 @@ const tdoa_kparams *tdoa_ctx_kparams(const tdoa_ctx *c);
 int tdoa_ctx_device(const tdoa_ctx *c);
 int tdoa_ctx_engine(const tdoa_ctx *c);
 int tdoa_ctx_rate(const tdoa_ctx *c);
+float tdoa_ctx_phat_eps(const tdoa_ctx *c);

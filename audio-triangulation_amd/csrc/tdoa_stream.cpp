@@ -6,8 +6,11 @@
 //   counter alternates between two slots by hop parity: the trigger zeroes the
 //   other slot for the next hop (a memset node cost 3.9 us per hop), so the
 //   two parities are two captured graphs.
+// A GCC_PHAT pipeline runs the same trigger, then k_stream_phat
+// (tdoa_stream_phat.hip): float scores, float EMA state, max_Lf.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 
@@ -15,11 +18,19 @@
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
 
+// a step's outputs, either engine's: tdoa_stream_outputs with max_L null and
+// max_Lf set for a GCC_PHAT pipeline (tdoa_stream_outputs_f)
+struct step_out {
+    tdoa_stream_outputs o{};
+    float *max_Lf = nullptr;
+};
+
 // a captured step graph and what it was captured for
 struct step_graph {
     hipGraphExec_t exec = nullptr;
     hipGraph_t graph = nullptr;
-    tdoa_stream_outputs out{};
+    step_out out{};
+    const float *bin_w = nullptr;  // GCC_PHAT: the context's weight table at capture
     hipStream_t stream = nullptr;
     step_graph() = default;
     step_graph(const step_graph &) = delete;
@@ -46,29 +57,32 @@ struct tdoa_stream {
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
     step_graph g[2];  // one per counter parity; released before mem
+    bool phat = false;      // GCC_PHAT pipeline: k_stream_phat after the trigger
+    float *est_f = nullptr; // ... its EMA state [S][P][K] (sp.est is null)
+    float phat_eps = 0.0f;
+    int phat_grid = 1;      // k_stream_phat's launch size
 };
 
 namespace {
 
-tdoa_stream_kout to_kout(const tdoa_stream_outputs *o)
+tdoa_stream_kout to_kout(const step_out &so)
 {
+    const tdoa_stream_outputs *o = &so.o;
     tdoa_stream_kout k{};
-    if (o) {
-        k.count = o->count;
-        k.stream_id = o->stream_id;
-        k.end = o->end;
-        k.lags = o->lags;
-        k.gate = o->gate;
-        k.ema_best = o->ema_best;
-        k.cell = o->cell;
-        k.xy = o->xy;
-        k.max_L = o->max_L;
-    }
+    k.count = o->count;
+    k.stream_id = o->stream_id;
+    k.end = o->end;
+    k.lags = o->lags;
+    k.gate = o->gate;
+    k.ema_best = o->ema_best;
+    k.cell = o->cell;
+    k.xy = o->xy;
+    k.max_L = o->max_L;
     return k;
 }
 
 // the per-hop kernel sequence; par: the hop's counter slot
-int enqueue_step(tdoa_stream *st, const tdoa_stream_outputs *out, hipStream_t s, int par)
+int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
 {
     tdoa_stream_params sp = st->sp;
     sp.count = st->sp.count + par;
@@ -77,6 +91,16 @@ int enqueue_step(tdoa_stream *st, const tdoa_stream_outputs *out, hipStream_t s,
     int rc = tdoa_launch_stream_trigger(sp, st->S, s, &by_id);
     if (rc)
         return rc;
+    if (st->phat) {
+        // the weight table in force on the context now (tdoa_set_bin_weights)
+        tdoa_kparams kp = st->kp;
+        const tdoa_kparams *ck = tdoa_ctx_kparams(st->ctx);
+        kp.bin_w = ck->bin_w;
+        kp.bin_lo = ck->bin_lo;
+        kp.bin_hi = ck->bin_hi;
+        return tdoa_launch_stream_phat(sp, kp, to_kout(out), st->est_f, out.max_Lf, st->S, by_id, st->phat_eps,
+                                       st->phat_grid, s);
+    }
     tdoa_kparams kp = st->kp;
     if (by_id) {  // listed only: DIRECT stages each frame from its stream's ring
         kp.frame_ids = sp.ids;
@@ -119,10 +143,17 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     if (!ctx || !out || !capture)
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: NULL argument");
     *out = nullptr;
-    if (tdoa_ctx_engine(ctx) != TDOA_ENGINE_DIRECT)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: needs a DIRECT context");
+    const int engine = tdoa_ctx_engine(ctx);
+    if (engine != TDOA_ENGINE_DIRECT && engine != TDOA_ENGINE_GCC_PHAT)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: needs a DIRECT or GCC_PHAT context");
+    const bool phat = engine == TDOA_ENGINE_GCC_PHAT;
     const tdoa_kparams &kp = *tdoa_ctx_kparams(ctx);
     const int M = kp.M, N = kp.N, P = kp.P, K = kp.K;
+    if (phat && !tdoa_stream_phat_fits(kp))
+        return tdoa_fail(TDOA_ERR_INVALID,
+                         "tdoa_stream_create: GCC_PHAT with %d mics x frame_len %d needs %zu bytes of LDS per "
+                         "workgroup (limit 160 KiB)",
+                         M, N, tdoa_stream_phat_lds(kp));
     if (num_streams < 1)
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: num_streams %d < 1", num_streams);
     if (hop < 1 || hop > N || hop > 4096)
@@ -141,6 +172,13 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->S = num_streams;
     st->kp = kp;
     st->use_graph = use_graph;
+    st->phat = phat;
+    if (phat) {
+        st->phat_eps = tdoa_ctx_phat_eps(ctx);
+        // TDOA_STREAM_PHAT_GRID=n caps k_stream_phat's launch size (A/B runs)
+        const char *cap = std::getenv("TDOA_STREAM_PHAT_GRID");
+        st->phat_grid = tdoa_stream_phat_grid(kp, num_streams, cap ? std::atoi(cap) : 0);
+    }
     const size_t S = (size_t)num_streams;
     // carve: 256-B aligned sub-buffers of one allocation
     size_t off = 0;
@@ -149,10 +187,12 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
         off = (off + bytes + 255) & ~(size_t)255;
         return o;
     };
+    // (a GCC_PHAT pipeline keeps the frame's scores on chip: no fresh* buffers, float EMA state)
     const size_t o_pos = take(8), o_count = take(8), o_rs = take(S * 8), o_ids = take(S * 4),
-                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(S * M * N), o_fresh = take(S * P * K * 8),
-                 o_fl = take(S * P * 4), o_fg = take(S), o_est = take(S * P * K * 8),
-                 o_last = take(S * 8), o_stats = take(16);
+                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(S * M * N),
+                 o_fresh = take(phat ? 0 : S * P * K * 8), o_fl = take(phat ? 0 : S * P * 4),
+                 o_fg = take(phat ? 0 : S), o_est = take(S * P * K * (phat ? 4 : 8)), o_last = take(S * 8),
+                 o_stats = take(16);
     if (st->mem.alloc(off) != hipSuccess)
         return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_create: %zu bytes of stream state", off);
     char *b = st->mem.get<char>();
@@ -171,10 +211,11 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.end = (int64_t *)(b + o_end);
     sp.ring_at = (int64_t *)(b + o_at);
     sp.frames = (int16_t *)(b + o_frames);
-    sp.fresh = (int64_t *)(b + o_fresh);
-    sp.fresh_lags = (int32_t *)(b + o_fl);
-    sp.fresh_gate = (uint8_t *)(b + o_fg);
-    sp.est = (int64_t *)(b + o_est);
+    sp.fresh = phat ? nullptr : (int64_t *)(b + o_fresh);
+    sp.fresh_lags = phat ? nullptr : (int32_t *)(b + o_fl);
+    sp.fresh_gate = phat ? nullptr : (uint8_t *)(b + o_fg);
+    sp.est = phat ? nullptr : (int64_t *)(b + o_est);
+    st->est_f = phat ? (float *)(b + o_est) : nullptr;
     sp.last = (uint64_t *)(b + o_last);
     sp.stats = (int64_t *)(b + o_stats);
     if (hipMemset(st->mem.get<void>(), 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
@@ -183,10 +224,10 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     return TDOA_OK;
 }
 
-extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out, void *stream)
+namespace {
+
+int stream_step(tdoa_stream *st, const step_out &out, void *stream)
 {
-    if (!st)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step: NULL stream");
     HIP_TRY(hipSetDevice(st->device));
     hipStream_t s = (hipStream_t)stream;
     const int par = (int)(st->hop & 1);
@@ -202,9 +243,12 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
         }
         return rc;
     }
-    const tdoa_stream_outputs want = out ? *out : tdoa_stream_outputs{};
+    const step_out &want = out;
+    // the weight table is a kernel argument: a graph captured under another one is stale
+    const float *bin_w = st->phat ? tdoa_ctx_kparams(st->ctx)->bin_w : nullptr;
     step_graph &sg = st->g[par];
-    if (!sg.exec || sg.stream != s || std::memcmp(&want, &sg.out, sizeof want) != 0) {
+    if (!sg.exec || sg.stream != s || sg.bin_w != bin_w || std::memcmp(&want.o, &sg.out.o, sizeof want.o) != 0 ||
+        want.max_Lf != sg.out.max_Lf) {
         sg.drop();
         HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         const int rc = enqueue_step(st, out, s, par);
@@ -220,6 +264,7 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
         sg.graph = g;
         HIP_TRY(hipGraphInstantiate(&sg.exec, g, nullptr, nullptr, 0));
         sg.out = want;
+        sg.bin_w = bin_w;
         sg.stream = s;
     }
     const hipError_t el = hipGraphLaunch(sg.exec, s);
@@ -233,6 +278,41 @@ extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out,
     return TDOA_OK;
 }
 
+}  // namespace
+
+extern "C" int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out, void *stream)
+{
+    if (!st)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step: NULL stream");
+    if (st->phat)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step: a GCC_PHAT pipeline steps with tdoa_stream_step_f");
+    step_out so;
+    if (out)
+        so.o = *out;
+    return stream_step(st, so, stream);
+}
+
+extern "C" int tdoa_stream_step_f(tdoa_stream *st, const tdoa_stream_outputs_f *out, void *stream)
+{
+    if (!st)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step_f: NULL stream");
+    if (!st->phat)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_step_f: a DIRECT pipeline steps with tdoa_stream_step");
+    step_out so;
+    if (out) {
+        so.o.count = out->count;
+        so.o.stream_id = out->stream_id;
+        so.o.end = out->end;
+        so.o.lags = out->lags;
+        so.o.gate = out->gate;
+        so.o.ema_best = out->ema_best;
+        so.o.cell = out->cell;
+        so.o.xy = out->xy;
+        so.max_Lf = out->max_Lf;
+    }
+    return stream_step(st, so, stream);
+}
+
 extern "C" int tdoa_stream_reset(tdoa_stream *st, void *stream)
 {
     if (!st)
@@ -243,24 +323,49 @@ extern "C" int tdoa_stream_reset(tdoa_stream *st, void *stream)
     return TDOA_OK;
 }
 
-extern "C" int tdoa_stream_state(tdoa_stream *st, int64_t *pos, int64_t *est, uint64_t *last,
-                                 int64_t *stats)
+namespace {
+
+// est: int64 [S][P][K] of a DIRECT pipeline or float of a GCC_PHAT one
+int stream_state(tdoa_stream *st, int64_t *pos, void *est, uint64_t *last, int64_t *stats)
 {
-    if (!st)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state: NULL stream");
     HIP_TRY(hipSetDevice(st->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t S = (size_t)st->S;
     if (pos)
         HIP_TRY(hipMemcpy(pos, st->sp.pos, sizeof(int64_t), hipMemcpyDeviceToHost));
     if (est)
-        HIP_TRY(hipMemcpy(est, st->sp.est, S * st->kp.P * st->kp.K * sizeof(int64_t),
-                        hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(est, st->phat ? (const void *)st->est_f : (const void *)st->sp.est,
+                          S * st->kp.P * st->kp.K * (st->phat ? sizeof(float) : sizeof(int64_t)),
+                          hipMemcpyDeviceToHost));
     if (last)
         HIP_TRY(hipMemcpy(last, st->sp.last, S * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (stats)
         HIP_TRY(hipMemcpy(stats, st->sp.stats, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
     return TDOA_OK;
+}
+
+}  // namespace
+
+extern "C" int tdoa_stream_state(tdoa_stream *st, int64_t *pos, int64_t *est, uint64_t *last,
+                                 int64_t *stats)
+{
+    if (!st)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state: NULL stream");
+    if (st->phat && est)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state: a GCC_PHAT pipeline's scores are float "
+                                           "(tdoa_stream_state_f)");
+    return stream_state(st, pos, est, last, stats);
+}
+
+extern "C" int tdoa_stream_state_f(tdoa_stream *st, int64_t *pos, float *est, uint64_t *last,
+                                   int64_t *stats)
+{
+    if (!st)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state_f: NULL stream");
+    if (!st->phat)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state_f: a DIRECT pipeline's scores are int64 "
+                                           "(tdoa_stream_state)");
+    return stream_state(st, pos, est, last, stats);
 }
 
 extern "C" int tdoa_stream_destroy(tdoa_stream *st)

@@ -1,0 +1,467 @@
+// tdoa_stream_phat.hip -- the streaming hop of a GCC_PHAT pipeline after the
+// trigger (tdoa_stream.hip): what k_direct_mfma's fused EMA form does for
+// DIRECT, as one kernel.
+//
+//   k_stream_phat  one 256-thread workgroup per triggered slot, persistent over
+//                  the device-side count.  Per slot: the frame's 8-bit samples
+//                  from the capture ring (k_stream_trigger_p lists the firing
+//                  streams only) or from the trigger's compact copy; per mic
+//                  the integer front end, the complex FFT_N of z[n] = x[2n] +
+//                  i x[2n+1] in LDS, the real-FFT split and the PHAT unit
+//                  spectrum U_m = X_m / sqrt(|X_m|^2 + eps), kept in LDS for
+//                  all M mics; per pair R = conj(U_i) U_j (times the context's
+//                  per-bin weights when a table is in force), the inverse FFT
+//                  in one work buffer, lags -S..S, first maximum, lag prior;
+//                  gate; for gated frames the float EMA on the stream's scores
+//                      est <- est + (fresh - est) * decay(now, last[s])
+//                  (fp32, no contraction; now = end * 1e6 / fs), the EMA rows'
+//                  first maxima and the grid solve on the EMA scores over the
+//                  distinct lag tuples (float L, first tuple on ties).
+//
+// The FFT, the split and the front end are tdoa_phat_split.hip's (one copy,
+// tdoa_phat_lds.h); the unit spectra, the pre-twiddle and the argmax are
+// k_phat_spectra's / k_phat_pairs_w's expressions, so a frame's scores are
+// those of the two-pass route.  Samples stay in int16 units (eps x 2^30).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <climits>
+
+#include "tdoa_internal.h"
+#include "tdoa_phat_lds.h"
+
+
+namespace {
+
+// diagnostic build only (libtdoa_diag.so): s_memtime cycles per phase summed by
+// each workgroup's thread 0 over its slots of the last hop -- [0] staging,
+// [1] front ends and forward FFTs, [2] pairs, [3] EMA and grid, [4] slots
+#ifdef TDOA_DIAG
+#define SP_DIAG_WG 4096
+__device__ unsigned long long g_diag_sp[SP_DIAG_WG * 8];
+#define SP_T0() unsigned long long sp_t_ = __builtin_amdgcn_s_memtime(), sp_acc_[5] = {0, 0, 0, 0, 0}
+#define SP_MARK(k)                                                  \
+    do {                                                            \
+        const unsigned long long n_ = __builtin_amdgcn_s_memtime(); \
+        sp_acc_[k] += n_ - sp_t_;                                   \
+        sp_t_ = n_;                                                 \
+    } while (0)
+#define SP_FLUSH()                                                           \
+    do {                                                                     \
+        if (threadIdx.x == 0 && blockIdx.x < SP_DIAG_WG)                     \
+            for (int k_ = 0; k_ < 5; k_++)                                   \
+                g_diag_sp[(size_t)blockIdx.x * 8 + k_] = sp_acc_[k_];        \
+    } while (0)
+#else
+#define SP_T0() \
+    do {        \
+    } while (0)
+#define SP_MARK(k) \
+    do {           \
+    } while (0)
+#define SP_FLUSH() \
+    do {           \
+    } while (0)
+#endif
+
+// correlations.c:44-47 on float scores: one EMA step, rounded step by step
+__device__ __forceinline__ float ema_step(float est, float fresh, float dec)
+{
+#pragma clang fp contract(off)
+    const float delta = (fresh - est) * dec;
+    return est + delta;
+}
+
+// first maximum of row[0..K) (K <= 127) over one wave: two candidates per lane
+// in ascending order, strict '>' keeps the first; the same index in every lane
+__device__ __forceinline__ int wave_first_max(float v1, float v2, int lane, int K)
+{
+    const int k1 = lane, k2 = lane + 64;
+    float bv = v1;
+    int bk = k1 < K ? k1 : INT_MAX;
+    if (k2 < K && (v2 > bv || bk == INT_MAX)) {
+        bv = v2;
+        bk = k2;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int ok = __shfl_xor(bk, o, 64);
+        if (ov > bv || (ov == bv && ok < bk) || (bk == INT_MAX && ok != INT_MAX)) {
+            bv = ov;
+            bk = ok;
+        }
+    }
+    bk = __shfl(bk, 0, 64);
+    return bk < 0 ? 0 : (bk >= K ? K - 1 : bk);  // NaN scores: keep the index in range
+}
+
+__global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa_kparams kp, tdoa_stream_kout out,
+                                                     float *__restrict__ est_all, float *__restrict__ max_Lf,
+                                                     int nstreams, int by_id, float e2)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = kp.N, NW = N / 2, M = kp.M, P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, nwaves = TPB / 64;
+    f2 *U = (f2 *)smem;                // [M][N] unit spectra (slot 0 = bins 0 and N); a mic's raw samples before
+    f2 *buf = U + (size_t)M * N;       // [N] FFT work buffer
+    float *Wf = (float *)(buf + N);    // [P][K] the frame's weighted scores
+    float *E = Wf + P * K;             // [P][K] the stream's EMA scores
+    __shared__ int red[TPB / 64];
+    __shared__ float redv[TPB / 64];
+    __shared__ int redi[TPB / 64];
+    __shared__ float sc[128];
+    __shared__ int lag_s[TDOA_MAX_PAIRS];
+
+    // at most one slot per stream: a corrupted counter cannot index past [S]
+    const int cnt_raw = *sp.count;
+    const int cnt = cnt_raw < 0 ? 0 : (cnt_raw > nstreams ? nstreams : cnt_raw);
+    if (blockIdx.x == 0 && tid == 0) {
+        *sp.pos += sp.H;  // the trigger kernel has read it
+        sp.stats[0] += cnt;
+        if (out.count)
+            *out.count = cnt;
+    }
+    const uint32_t *win = reinterpret_cast<const uint32_t *>(kp.window);
+    const int64_t ring_bytes = sp.capture_len * M;
+    int ngated = 0;  // this workgroup's gated frames
+    SP_T0();
+    // persistent over the compact batch (its size is only known on the device)
+    for (int slot = blockIdx.x; slot < cnt; slot += gridDim.x) {
+        __syncthreads();  // the previous slot's tables and reductions are consumed
+        SP_MARK(3);
+        const int s = sp.ids[slot];
+        const int64_t end = sp.end[slot];
+
+        // ---- the frame's 8-bit samples, widened, mic m's row at the start of U[m]
+        if (by_id) {
+            // ring bytes [at * M, at * M + N * M) of the stream, wrapping at the
+            // ring's end; byte loads: a ring need not start 4-byte aligned
+            const uint8_t *cap = sp.capture + (size_t)s * ring_bytes;
+            const int64_t b0 = sp.ring_at[slot] * M;
+            for (int i = tid; i < N * M; i += TPB) {
+                const int l = i / M, m = i - l * M;
+                int64_t b = b0 + i;
+                if (b >= ring_bytes)
+                    b -= ring_bytes;
+                reinterpret_cast<int16_t *>(U + (size_t)m * N)[l] = (int16_t)cap[b];
+            }
+        } else {
+            const uint32_t *src =
+                reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(sp.frames) + (size_t)slot * M * N);
+            for (int i = tid; i < M * N / 4; i += TPB) {
+                const int m = (4 * i) / N, n = 4 * i - m * N;
+                const uint32_t w = src[i];
+                uint32_t *dst = reinterpret_cast<uint32_t *>(U + (size_t)m * N) + (n >> 1);
+                dst[0] = (w & 0xFFu) | ((w >> 8) & 0xFFu) << 16;
+                dst[1] = ((w >> 16) & 0xFFu) | (w >> 24) << 16;
+            }
+        }
+        __syncthreads();
+        SP_MARK(0);
+
+        // ---- per mic: front end, FFT_N, split, unit spectrum
+        for (int m = 0; m < M; m++) {
+            const uint32_t *x = reinterpret_cast<const uint32_t *>(U + (size_t)m * N);
+            int sum = 0;
+            for (int w = tid; w < NW; w += TPB) {
+                const uint32_t v = x[w];
+                sum += (int)(int16_t)(v & 0xFFFFu) + (int)(int16_t)(v >> 16);
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1)
+                sum += __shfl_xor(sum, o, 64);
+            if (lane == 0)
+                red[wave] = sum;
+            __syncthreads();
+            int tot = 0;
+#pragma unroll
+            for (int w = 0; w < TPB / 64; w++)
+                tot += red[w];
+            const uint32_t off16 = (uint32_t)(tot >> kp.log2N) & 0xFFFFu;  // floor mean, (int16)
+            for (int w = tid; w < N; w += TPB) {
+                f2 z = f2{0.0f, 0.0f};
+                if (w < NW) {
+                    const uint32_t p = prep_word(x[w], off16, win[w]);
+                    z = f2{(float)(int16_t)(p & 0xFFFFu), (float)(int16_t)(p >> 16)};
+                }
+                buf[w] = z;
+            }
+            __syncthreads();
+            fft_inplace<false>(buf, N, kp.tw);
+
+            // X[k] = (Z[k] + Z*[N-k])/2 - i/2 W_2N^k (Z[k] - Z*[N-k]), then U = X / sqrt(|X|^2 + e2)
+            f2 *o = U + (size_t)m * N;
+            for (int k = tid; k <= N / 2; k += TPB) {
+                const int kn = (N - k) & (N - 1);
+                const f2 a = buf[k], b = buf[kn];
+                if (k == 0) {  // X[0], X[N]: both real
+                    const float x0 = a.x + a.y, xn = a.x - a.y;
+                    o[0] = f2{x0 * __builtin_amdgcn_rsqf(x0 * x0 + e2), xn * __builtin_amdgcn_rsqf(xn * xn + e2)};
+                    continue;
+                }
+                const f2 w2k = ldtw(kp.tw2, k), w2n = ldtw(kp.tw2, N - k);
+                const f2 e = a + conj2(b), d = cmul(w2k, a - conj2(b));
+                f2 xk = 0.5f * f2{e.x + d.y, e.y - d.x};
+                xk *= __builtin_amdgcn_rsqf(xk.x * xk.x + xk.y * xk.y + e2);
+                o[k] = xk;
+                if (k != N / 2) {
+                    const f2 ee = b + conj2(a), dd = cmul(w2n, b - conj2(a));
+                    f2 xn = 0.5f * f2{ee.x + dd.y, ee.y - dd.x};
+                    xn *= __builtin_amdgcn_rsqf(xn.x * xn.x + xn.y * xn.y + e2);
+                    o[kn] = xn;
+                }
+            }
+            __syncthreads();  // buf and red are free for the next mic
+        }
+
+        SP_MARK(1);
+        // ---- per pair: cross spectrum, inverse FFT_N, lags -S..S, first maximum, prior
+        const float *bw = kp.bin_w;
+        for (int p = 0; p < P; p++) {
+            const f2 *Ui = U + (size_t)kp.pair_i[p] * N;
+            const f2 *Uj = U + (size_t)kp.pair_j[p] * N;
+            // R = conj(U_i) U_j;  Y[k] = (R[k] + R*[N-k]) + i (R[k] - R*[N-k]) conj(W_2N^k)
+            for (int k = tid; k <= N / 2; k += TPB) {
+                const int kn = (N - k) & (N - 1);
+                f2 ik = Ui[k], in = Ui[kn], jk = Uj[k], jn = Uj[kn];
+                if (k == 0) {  // slot 0 = (U[0], U[N]), both real
+                    ik = f2{ik.x, 0.0f};
+                    jk = f2{jk.x, 0.0f};
+                    in = f2{in.y, 0.0f};
+                    jn = f2{jn.y, 0.0f};
+                }
+                f2 Rk = cmul(conj2(ik), jk), Rn = cmul(conj2(in), jn);
+                if (bw) {  // band-limited: bin k by w[k], bin N - k by w[N - k]
+                    Rk = bw[k] * Rk;
+                    Rn = bw[N - k] * Rn;
+                }
+                const f2 w2k = ldtw(kp.tw2, k), w2n = ldtw(kp.tw2, N - k);
+                buf[k] = (Rk + conj2(Rn)) + mul_i(cmul(Rk - conj2(Rn), conj2(w2k)));
+                if (k != 0 && k != N / 2)
+                    buf[kn] = (Rn + conj2(Rk)) + mul_i(cmul(Rn - conj2(Rk), conj2(w2n)));
+            }
+            __syncthreads();
+            fft_inplace<true>(buf, N, kp.tw);
+
+            // r[s] = y / 2N at s mod 2N:  r[2u] = Re y[u], r[2u+1] = Im y[u]
+            const float invL = 1.0f / (float)(2 * N);
+            for (int i = tid; i < K; i += TPB) {
+                const int sh = i - S;
+                const int mm = sh < 0 ? sh + 2 * N : sh;
+                const f2 y = buf[mm >> 1];
+                sc[i] = ((mm & 1) ? y.y : y.x) * invL;
+            }
+            __syncthreads();
+            if (tid < 64) {
+                const int k1 = lane, k2 = lane + 64;
+                const float v1 = k1 < K ? sc[k1] : -INFINITY, v2 = k2 < K ? sc[k2] : -INFINITY;
+                const int bk = wave_first_max(v1, v2, lane, K);
+                if (k1 < K)
+                    Wf[p * K + k1] = v1 * kp.prior[k1 > bk ? k1 - bk : bk - k1];
+                if (k2 < K)
+                    Wf[p * K + k2] = v2 * kp.prior[k2 > bk ? k2 - bk : bk - k2];
+                if (lane == 0)
+                    lag_s[p] = bk - S;
+            }
+            __syncthreads();  // sc and buf are free for the next pair
+        }
+
+        SP_MARK(2);
+#ifdef TDOA_DIAG
+        sp_acc_[4] += 1;
+#endif
+        // ---- gate and the slot's record
+        int g2 = 0;
+        for (int p = 0; p < P; p++)
+            g2 += lag_s[p] * lag_s[p];
+        const bool gated = g2 > 4;  // sample_compute.h:124-134
+        if (out.lags) {
+            for (int p = tid; p < P; p += TPB)
+                out.lags[(size_t)slot * P + p] = lag_s[p];
+        }
+        if (tid == 0) {
+            if (out.stream_id)
+                out.stream_id[slot] = s;
+            if (out.end)
+                out.end[slot] = end;
+            if (out.gate)
+                out.gate[slot] = gated ? 1 : 0;
+        }
+        if (!gated) {  // sample_compute.h:134: only gated frames update
+            if (tid == 0 && out.cell)
+                out.cell[slot] = -1;
+            continue;
+        }
+        ngated++;
+
+        // ---- float EMA on the stream's scores, the rows' first maxima
+        const uint64_t now = (uint64_t)end * 1000000u / (uint64_t)sp.fs;
+        const float dec = tdoa_decay_dev(now, sp.last[s]);
+        float *est = est_all + (size_t)s * P * K;
+        for (int i = tid; i < P * K; i += TPB) {
+            const float nv = ema_step(est[i], Wf[i], dec);
+            est[i] = nv;
+            E[i] = nv;
+        }
+        __syncthreads();
+        if (tid == 0)
+            sp.last[s] = now;
+        if (out.ema_best) {
+            for (int p = wave; p < P; p += nwaves) {
+                const int k1 = lane, k2 = lane + 64;
+                const float v1 = k1 < K ? E[p * K + k1] : -INFINITY, v2 = k2 < K ? E[p * K + k2] : -INFINITY;
+                const int bk = wave_first_max(v1, v2, lane, K);
+                if (lane == 0)
+                    out.ema_best[(size_t)slot * P + p] = bk - S;
+            }
+        }
+
+        // ---- grid solve on the EMA scores over the distinct lag tuples
+        float bv = -INFINITY;
+        int bu = INT_MAX;
+        if (kp.TW == 1) {
+            // 3-4 mic grids: a thread's tuple words are loaded 8 at a time ahead of
+            // their gathers (one L2 round trip per 8 tuples, not per tuple)
+            for (int u0 = tid; u0 < kp.U; u0 += 8 * TPB) {
+                uint32_t wd[8];
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const int u = u0 + t * TPB;
+                    wd[t] = u < kp.U ? kp.tuples[u] : 0u;
+                }
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const int u = u0 + t * TPB;
+                    if (u < kp.U) {
+                        float Lv = 0.0f;
+                        for (int p = 0; p < P; p++)
+                            Lv += E[p * K + ((wd[t] >> (8 * p)) & 0xFFu)];
+                        if (Lv > bv) {  // ascending u per thread: strict '>' keeps the first
+                            bv = Lv;
+                            bu = u;
+                        }
+                    }
+                }
+            }
+        } else {
+            for (int u = tid; u < kp.U; u += TPB) {
+                float Lv = 0.0f;
+                for (int tw = 0; tw < kp.TW; tw++) {
+                    const uint32_t word = kp.tuples[u * kp.TW + tw];
+                    for (int b = 0; b < 4; b++) {
+                        const int p = 4 * tw + b;
+                        if (p < P)
+                            Lv += E[p * K + ((word >> (8 * b)) & 0xFFu)];
+                    }
+                }
+                if (Lv > bv) {
+                    bv = Lv;
+                    bu = u;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int ou = __shfl_xor(bu, o, 64);
+            if (ov > bv || (ov == bv && ou < bu)) {
+                bv = ov;
+                bu = ou;
+            }
+        }
+        if (lane == 0) {
+            redv[wave] = bv;
+            redi[wave] = bu;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < nwaves; w++)
+                if (redv[w] > bv || (redv[w] == bv && redi[w] < bu)) {
+                    bv = redv[w];
+                    bu = redi[w];
+                }
+            if (bu < 0 || bu >= kp.U)  // NaN scores: keep the index in range
+                bu = 0;
+            const int cell = kp.tuple_cell[bu];
+            if (out.cell)
+                out.cell[slot] = cell;
+            if (max_Lf)
+                max_Lf[slot] = bv;
+            if (out.xy) {
+                const int cx = cell % kp.grid_W, cy = cell / kp.grid_W;
+                out.xy[2 * slot] = (float)(cx - kp.half_w) / kp.grid_scale;
+                out.xy[2 * slot + 1] = (float)(kp.half_h - cy) / kp.grid_scale;
+            }
+        }
+    }
+    SP_MARK(3);
+    SP_FLUSH();
+    // gated frames of this hop: one atomic per workgroup that had any
+    if (tid == 0 && ngated)
+        atomicAdd(reinterpret_cast<unsigned long long *>(sp.stats + 1), (unsigned long long)ngated);
+}
+
+int fail_hip(hipError_t e, const char *what)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
+    return tdoa_set_error(-2, buf);
+}
+
+}  // namespace
+
+#ifdef TDOA_DIAG
+extern "C" int tdoa_diag_fetch_stream_phat(unsigned long long *host, int n)
+{
+    if (n > SP_DIAG_WG * 8)
+        n = SP_DIAG_WG * 8;
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_diag_sp), sizeof(unsigned long long) * n, 0,
+                               hipMemcpyDeviceToHost) == hipSuccess
+               ? 0
+               : -2;
+}
+#endif
+
+size_t tdoa_stream_phat_lds(const tdoa_kparams &kp)
+{
+    return (size_t)kp.M * kp.N * 8 + (size_t)kp.N * 8 + 2 * (size_t)kp.P * kp.K * 4;
+}
+
+// 160 KiB per workgroup, less the kernel's static tables (under 1 KiB)
+static constexpr size_t LDS_BUDGET = 160 * 1024 - 1024;
+
+bool tdoa_stream_phat_fits(const tdoa_kparams &kp)
+{
+    return kp.N >= 256 && kp.N <= 4096 && !(kp.N & (kp.N - 1)) && kp.K <= 127 &&
+           tdoa_stream_phat_lds(kp) <= LDS_BUDGET;
+}
+
+int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap)
+{
+    const int res = tdoa_resident_blocks((const void *)k_stream_phat, TPB, tdoa_stream_phat_lds(kp));
+    int64_t grid = S;
+    if (res > 0 && grid > res)
+        grid = res;
+    if (cap > 0 && grid > cap)
+        grid = cap;
+    return (int)(grid > 0 ? grid : 1);
+}
+
+int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
+                            float *est, float *max_Lf, int64_t S, bool by_id, float phat_eps, int grid,
+                            void *stream)
+{
+    if (!tdoa_stream_phat_fits(kp))
+        return tdoa_set_error(-1, "stream GCC_PHAT: shape exceeds the LDS budget");
+    // the per-mic floor as tdoa_launch_gcc_phat passes it to k_phat_spectra's
+    // consumers: a normal float, in int16 units
+    float eps = phat_eps;
+    if (!(eps >= 1e-30f))
+        eps = 1e-30f;
+    hipLaunchKernelGGL(k_stream_phat, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TPB), tdoa_stream_phat_lds(kp),
+                       (hipStream_t)stream, sp, kp, out, est, max_Lf, (int)S, by_id ? 1 : 0,
+                       eps * 1073741824.0f /* 2^30: int16 units */);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail_hip(e, "k_stream_phat launch");
+}

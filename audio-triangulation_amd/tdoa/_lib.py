@@ -29,7 +29,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_get_prior", "tdoa_dpss_q15", "tdoa_last_error", "tdoa_abi_version", "tdoa_batch_kernel",
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
-    "tdoa_stream_destroy",
+    "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     # tdoa_reference_abi.h
     "microphones_init", "rolling_buffer_init", "rolling_buffer_push",
@@ -85,6 +85,12 @@ class StreamOutputs(C.Structure):
     """struct tdoa_stream_outputs (include/tdoa.h): device pointers."""
     _fields_ = [(n, C.c_void_p) for n in (
         "count", "stream_id", "end", "lags", "gate", "ema_best", "cell", "xy", "max_L")]
+
+
+class StreamOutputsF(C.Structure):
+    """struct tdoa_stream_outputs_f (a GCC_PHAT pipeline): device pointers."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "count", "stream_id", "end", "lags", "gate", "ema_best", "cell", "xy", "max_Lf")]
 
 
 # reference structs (include/tdoa_reference_abi.h, reference buffer.h:8-12,
@@ -150,6 +156,8 @@ def load() -> C.CDLL:
     L.tdoa_stream_step.argtypes = [P, C.POINTER(StreamOutputs), P]
     L.tdoa_stream_reset.argtypes = [P, P]
     L.tdoa_stream_state.argtypes = [P, P, P, P, P]
+    L.tdoa_stream_step_f.argtypes = [P, C.POINTER(StreamOutputsF), P]
+    L.tdoa_stream_state_f.argtypes = [P, P, P, P, P]
     L.tdoa_stream_destroy.argtypes = [P]
     L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
     L.tdoa_set_bin_weights.argtypes = [P, P]

@@ -5,7 +5,13 @@ for S independent streams: every `step()` consumes one hop of H samples per
 stream from a device capture ring of 8-bit ADC bytes [S][capture_len][M]
 (dma_sampler.c:17-23), runs the trigger scan, the DIRECT path on the
 triggered frames, the EMA (correlations.c:38-63) and the grid solve on the
-EMA scores -- all libtdoa kernels, replayed as one hipGraph per step.
+EMA scores -- all libtdoa kernels, launched on the pipeline's stream (or, with
+use_graph, replayed as one hipGraph per step).
+
+A `gcc_phat` Localizer streams the GCC-PHAT engine instead (k_stream_phat):
+float scores under the localizer's weight table (set_band / set_bin_weights,
+read at every step), a float32 EMA, `out["max_Lf"]` in place of
+`out["max_L"]` and float32 `est` from state().
 """
 from __future__ import annotations
 
@@ -14,7 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import StreamOutputs, check, load
+from ._lib import StreamOutputs, StreamOutputsF, check, load
 from .localizer import Localizer
 
 
@@ -24,8 +30,9 @@ class StreamPipeline:
     # (tools/diag_stream_launch.py, same box; the graph's launch adds ~5 us)
     def __init__(self, loc: Localizer, capture: torch.Tensor, hop: int = 512,
                  use_graph: bool = False):
-        if loc.engine != "direct":
-            raise ValueError("the streaming pipeline runs the DIRECT engine")
+        if loc.engine not in ("direct", "gcc_phat"):
+            raise ValueError("the streaming pipeline runs the DIRECT or the GCC_PHAT engine")
+        self.phat = loc.engine == "gcc_phat"
         if capture.dtype != torch.uint8 or capture.dim() != 3 or capture.shape[2] != loc.dims.M:
             raise ValueError(f"capture must be uint8 [S][T][{loc.dims.M}]")
         if capture.device != loc.torch_device or not capture.is_contiguous():
@@ -44,9 +51,13 @@ class StreamPipeline:
             "ema_best": torch.zeros((S, P), dtype=torch.int32, device=dev),
             "cell": torch.zeros(S, dtype=torch.int32, device=dev),
             "xy": torch.zeros((S, 2), dtype=torch.float32, device=dev),
-            "max_L": torch.zeros(S, dtype=torch.int64, device=dev),
         }
-        self._s = StreamOutputs(*[self.out[n].data_ptr() for n, _ in StreamOutputs._fields_])
+        if self.phat:
+            self.out["max_Lf"] = torch.zeros(S, dtype=torch.float32, device=dev)
+        else:
+            self.out["max_L"] = torch.zeros(S, dtype=torch.int64, device=dev)
+        struct = StreamOutputsF if self.phat else StreamOutputs
+        self._s = struct(*[self.out[n].data_ptr() for n, _ in struct._fields_])
         # graph capture needs a real (non-default) stream
         self.stream = torch.cuda.Stream(device=dev)
         h = C.c_void_p()
@@ -57,8 +68,8 @@ class StreamPipeline:
 
     def step(self) -> dict:
         """One hop for every stream (asynchronous on self.stream)."""
-        check(load().tdoa_stream_step(self._h, C.byref(self._s),
-                                      C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_step")
+        step = load().tdoa_stream_step_f if self.phat else load().tdoa_stream_step
+        check(step(self._h, C.byref(self._s), C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_step")
         return self.out
 
     def records(self) -> dict:
@@ -76,11 +87,11 @@ class StreamPipeline:
     def state(self):
         P, K = self.loc.dims.P, self.loc.dims.K
         pos = np.zeros(1, np.int64)
-        est = np.zeros((self.S, P, K), np.int64)
+        est = np.zeros((self.S, P, K), np.float32 if self.phat else np.int64)
         last = np.zeros(self.S, np.uint64)
-        check(load().tdoa_stream_state(self._h, pos.ctypes.data_as(C.c_void_p),
-                                       est.ctypes.data_as(C.c_void_p),
-                                       last.ctypes.data_as(C.c_void_p), None), "tdoa_stream_state")
+        state = load().tdoa_stream_state_f if self.phat else load().tdoa_stream_state
+        check(state(self._h, pos.ctypes.data_as(C.c_void_p), est.ctypes.data_as(C.c_void_p),
+                    last.ctypes.data_as(C.c_void_p), None), "tdoa_stream_state")
         return int(pos[0]), est, last
 
     def totals(self):

@@ -293,7 +293,23 @@ int tdoa_dpss_q15(int32_t n, double nw, int32_t *out);
  * The step is a fixed kernel sequence reading its position from a device
  * clock, so with use_graph it is captured once into a hipGraph and replayed.
  * The producer keeps capture_len >= N + 2*hop samples of history per stream.
- * Requires a DIRECT context; hop <= N. */
+ * hop <= N.
+ *
+ * A GCC_PHAT context streams too: the same trigger, then per triggered frame
+ * the GCC-PHAT scores as tdoa_localize_batch defines them (the integer front
+ * end, U_m = X_m / sqrt(|X_m|^2 + phat_eps), r_ij = irfft(w conj(U_i) U_j),
+ * first maximum, lag prior, gate), with the per-bin weight table in force on
+ * the context at each step (tdoa_set_bin_weights / tdoa_set_band_hz: set it
+ * only while no step is in flight).  The EMA state is float:
+ *     est <- est + (fresh - est) * decay(now_us, last_us)     (fp32)
+ * on gated frames, and the grid solve runs on it in float (max_Lf).  Such a
+ * pipeline steps with tdoa_stream_step_f and is read with
+ * tdoa_stream_state_f; tdoa_stream_step, and tdoa_stream_state with a non-NULL
+ * est, return TDOA_ERR_INVALID on it, as the _f forms do on a DIRECT one.
+ * Accepted GCC_PHAT shapes: M * N * 8 + N * 8 + 2 * P * K * 4 bytes of LDS
+ * within 160 KiB (4 mics up to frame_len 2048, 8 mics up to 1024, ...);
+ * others are TDOA_ERR_INVALID.  TDOA_STREAM_PHAT_GRID=n in the environment at
+ * tdoa_stream_create caps the GCC_PHAT kernel's launch size (A/B runs). */
 typedef struct tdoa_stream tdoa_stream;
 
 typedef struct tdoa_stream_outputs { /* device pointers; slot order is arbitrary */
@@ -308,6 +324,18 @@ typedef struct tdoa_stream_outputs { /* device pointers; slot order is arbitrary
     int64_t *max_L;     /* [S] (gated slots)                                 */
 } tdoa_stream_outputs;
 
+typedef struct tdoa_stream_outputs_f { /* the same for a GCC_PHAT pipeline */
+    int32_t *count;
+    int32_t *stream_id;
+    int64_t *end;
+    int32_t *lags;
+    uint8_t *gate;
+    int32_t *ema_best;
+    int32_t *cell;
+    float *xy;
+    float *max_Lf;      /* [S] (gated slots)                                 */
+} tdoa_stream_outputs_f;
+
 int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
                        const uint8_t *capture, int64_t capture_len, int use_graph,
                        tdoa_stream **out);
@@ -315,6 +343,7 @@ int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
  * non-NULL stream; the captured graph is reused while `out` and `stream`
  * stay the same). */
 int tdoa_stream_step(tdoa_stream *st, const tdoa_stream_outputs *out, void *stream);
+int tdoa_stream_step_f(tdoa_stream *st, const tdoa_stream_outputs_f *out, void *stream);
 /* Back to the start: position 0, rings empty, EMA scores 0, EMA clocks 0. */
 int tdoa_stream_reset(tdoa_stream *st, void *stream);
 /* Synchronous snapshot: samples consumed, EMA scores [S][P][K], EMA clocks
@@ -322,6 +351,8 @@ int tdoa_stream_reset(tdoa_stream *st, void *stream);
  * may be NULL). */
 int tdoa_stream_state(tdoa_stream *st, int64_t *pos, int64_t *est, uint64_t *last,
                       int64_t *stats);
+int tdoa_stream_state_f(tdoa_stream *st, int64_t *pos, float *est, uint64_t *last,
+                        int64_t *stats);
 int tdoa_stream_destroy(tdoa_stream *st);
 
 const char *tdoa_last_error(void);

@@ -270,6 +270,11 @@ static tdoa_kout to_kout(const tdoa_outputs *o)
     return k;
 }
 
+int tdoa_hip_fail(hipError_t e, const char *what)
+{
+    return tdoa_fail(TDOA_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
 int tdoa_resident_blocks(const void *kernel, int threads, size_t lds)
 {
     static std::mutex mu;

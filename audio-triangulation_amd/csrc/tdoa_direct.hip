@@ -874,13 +874,6 @@ __global__ void __launch_bounds__(256) k_ref_buffer(int op, int16_t *__restrict_
 }
 
 
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return tdoa_set_error(-2, buf);
-}
-
 }  // namespace
 
 // Frames per workgroup and threads: F*items rounded to whole waves, chosen
@@ -1056,7 +1049,7 @@ int tdoa_launch_direct(const tdoa_kparams &kp_in, const tdoa_kout &out, const in
 #undef TDOA_LAUNCH_MF_CH
 #undef TDOA_LAUNCH_MF
         hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "k_direct_mfma launch");
+        return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_direct_mfma launch");
     }
     direct_geometry(kp, threads);
     const size_t lds = smem_bytes(kp, threads / 64);
@@ -1085,7 +1078,7 @@ int tdoa_launch_direct(const tdoa_kparams &kp_in, const tdoa_kout &out, const in
 #undef TDOA_LAUNCH_DIRECT
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return hip_fail(e, "k_direct launch");
+        return tdoa_hip_fail(e, "k_direct launch");
     return 0;
 }
 
@@ -1102,7 +1095,7 @@ int tdoa_launch_average(const tdoa_kparams &kp, int64_t S, int64_t *est, const i
                        est, fresh, decay, best, o, solve ? 1 : 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return hip_fail(e, "k_average launch");
+        return tdoa_hip_fail(e, "k_average launch");
     return 0;
 }
 
@@ -1116,7 +1109,7 @@ int tdoa_launch_ref_buffer(int op, int16_t *buf, const int16_t *ring, int head, 
                        head, power, window, n, log2n, s1, s2);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return hip_fail(e, "k_ref_buffer launch");
+        return tdoa_hip_fail(e, "k_ref_buffer launch");
     return 0;
 }
 

@@ -265,13 +265,6 @@ __global__ void __launch_bounds__(512) k_gcc_phat(tdoa_kparams kp, tdoa_kout out
 }
 
 
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return tdoa_set_error(-2, buf);
-}
-
 }  // namespace
 
 // ======================================================= GCC-PHAT, N = 1024
@@ -698,7 +691,7 @@ enum class PhatRoute { BAND, W64, P1K_LEAN, R16, SPLIT, FUSED_1024, GENERIC };
 static PhatRoute phat_route(const tdoa_kparams &kp)
 {
     // a weight table (tdoa_set_bin_weights): every shape takes the two-pass
-    // kernels with the weighted pass 2 (k_phat_spectra, k_phat_pairs_w)
+    // kernels with the weighted pass 2 (k_phat_spectra, k_phat_pairs<true>)
     if (kp.bin_w)
         return PhatRoute::BAND;
     if (use_w64(kp))
@@ -765,12 +758,8 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
                          int64_t B, float phat_eps, void *spec_scratch, size_t spec_bytes,
                          void *stream)
 {
-    // the per-mic floor of U_m = X_m / sqrt(|X_m|^2 + eps) (include/tdoa.h), x
-    // scaled by 2^-15; kept a normal float (v_rsq_f32 flushes denormals, and a
-    // zero bin must stay 0).  Each kernel gets it in the units of its own spectra.
-    float eps = phat_eps;
-    if (!(eps >= 1e-30f))
-        eps = 1e-30f;
+    // each kernel gets the per-mic floor in the units of its own spectra
+    // (tdoa_phat_floor, tdoa_phat_floor_int16)
     if (((uintptr_t)frames & 15) != 0)
         return tdoa_set_error(-1, "frames must be 16-byte aligned");
     if (!kp.tw || !kp.tw2)
@@ -785,9 +774,8 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
     if (route == PhatRoute::R16)
         return tdoa_launch_phat_r16(kp, out, frames, B, phat_eps, spec_scratch, spec_bytes, stream);
     if (route == PhatRoute::SPLIT || route == PhatRoute::BAND)
-        return tdoa_launch_gcc_phat_split(kp, out, frames, B,
-                                          eps * 1073741824.0f /* 2^30: int16 units */,
-                                          spec_scratch, spec_bytes, stream);
+        return tdoa_launch_gcc_phat_split(kp, out, frames, B, tdoa_phat_floor_int16(phat_eps), spec_scratch,
+                                          spec_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     if (route == PhatRoute::FUSED_1024) {
         // persistent 2-frame workgroups, as many as are resident at once
@@ -799,10 +787,11 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
         const int64_t iters = (npairs + resident - 1) / resident;
         const int64_t grid = (npairs + iters - 1) / iters;
         hipLaunchKernelGGL(k_gcc_phat_1024, dim3((unsigned)grid), dim3(192), lds1024, st, kp, out,
-                           frames, B, eps * 1073741824.0f /* 2^30: int16 units */);
+                           frames, B, tdoa_phat_floor_int16(phat_eps));
         hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "k_gcc_phat_1024 launch");
+        return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_gcc_phat_1024 launch");
     }
+    const float eps = tdoa_phat_floor(phat_eps);
     const int threads = kp.N / 4 < 64 ? 64 : kp.N / 4;
     if (threads != kp.N / 4)
         return tdoa_set_error(-1, "GCC_PHAT: frame_len must be >= 256");
@@ -822,7 +811,7 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return tdoa_set_error(-1, "GCC_PHAT: num_mics must be 2 or 3 for now");
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-        return hip_fail(e, "k_gcc_phat launch");
+        return tdoa_hip_fail(e, "k_gcc_phat launch");
     return 0;
 }
 

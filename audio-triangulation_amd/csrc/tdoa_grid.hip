@@ -371,13 +371,6 @@ bool tdoa_grid_bb_compact(const tdoa_kparams &kp)
     return bb_fits<float>(kp) && kp.wc_chunks != nullptr && kp.wc_CK > 0 && kp.wc_nch > 0;
 }
 namespace {
-int hip_fail(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return tdoa_set_error(-2, buf);
-}
-
 template <typename T, int TWC>
 void launch_gf(int gf, dim3 grid, dim3 block, size_t lds, hipStream_t st, const tdoa_kparams &kp,
                const tdoa_kout &out, const T *weighted, int64_t B, int CH)
@@ -430,7 +423,7 @@ int launch(const tdoa_kparams &kp, const tdoa_kout &out, const T *weighted, int6
         else
             launch_bb_jt<T, TWX>(kp, out, weighted, B, st);
         hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : hip_fail(e, "k_grid_bb launch");
+        return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_grid_bb launch");
     }
     if (kp.TW == 1)
         launch_gf<T, 1>(gf, dim3((unsigned)grid), dim3(threads), lds, st, kp, out, weighted, B, CH);
@@ -438,7 +431,7 @@ int launch(const tdoa_kparams &kp, const tdoa_kout &out, const T *weighted, int6
         launch_gf<T, TWX>(gf, dim3((unsigned)grid), dim3(threads), lds, st, kp, out, weighted, B,
                           CH);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "k_grid launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_grid launch");
 }
 
 // vga_heatmap.h:110-130 colouring pass as classes: 4 white (L >= 63/64 max),
@@ -489,7 +482,7 @@ int tdoa_launch_heatmap(const tdoa_kparams &kp, const void *weighted, const void
         hipLaunchKernelGGL(k_heatmap<int64_t>, grid, dim3(256), lds, st, kp,
                            (const int64_t *)weighted, (const int64_t *)max_L, classes);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(e, "k_heatmap launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_heatmap launch");
 }
 
 int tdoa_launch_grid(const tdoa_kparams &kp, const tdoa_kout &out, const void *weighted,

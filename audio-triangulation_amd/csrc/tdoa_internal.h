@@ -129,6 +129,22 @@ struct tdoa_stream_kout {
 // threads, LDS) under a mutex (contexts on different host threads / devices).
 int tdoa_resident_blocks(const void *kernel, int threads, size_t lds);
 
+// A failed launch or runtime call: "<what>: <HIP's text>" as the thread's last
+// error, returns TDOA_ERR_HIP (tdoa_capi.cpp).
+int tdoa_hip_fail(hipError_t e, const char *what);
+
+// The per-mic PHAT floor of U = X / sqrt(|X|^2 + eps) (include/tdoa.h) for x
+// scaled by 2^-15, kept a normal float (v_rsq_f32 flushes denormals, and a zero
+// bin must stay 0); and the same for kernels whose samples stay in int16 units,
+// where |X|^2 is 2^30 times as large.
+inline float tdoa_phat_floor(float phat_eps) { return phat_eps >= 1e-30f ? phat_eps : 1e-30f; }
+inline float tdoa_phat_floor_int16(float phat_eps) { return tdoa_phat_floor(phat_eps) * 1073741824.0f; }
+
+// Shapes the LDS Stockham kernels hold (tdoa_phat_lds.h: the two-pass route and
+// the streaming hop): N a power of two in [256, 4096], K = 2S + 1 <= 127 (two
+// argmax candidates per lane of one wave).
+inline bool tdoa_phat_lds_shape(int N, int K) { return N >= 256 && N <= 4096 && !(N & (N - 1)) && K <= 127; }
+
 // Host-side launchers implemented in the .hip files.
 // count_dev (optional): device int32 batch size, B then only bounds the grid.
 // ema (optional, streaming): the launch also runs the EMA of the gated frames

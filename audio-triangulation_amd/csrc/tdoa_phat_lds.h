@@ -1,11 +1,27 @@
-// tdoa_phat_lds.h -- the LDS pieces of GCC-PHAT that the two-pass kernels
-// (tdoa_phat_split.hip) and the streaming kernel (tdoa_stream_phat.hip) share:
-// the complex helpers, the in-place Stockham FFT of one 256-thread workgroup
-// and the integer front end of one packed sample pair.  Internal linkage per TU.
+// tdoa_phat_lds.h -- every LDS stage of GCC-PHAT that the two-pass kernels
+// (tdoa_phat_split.hip) and the streaming kernel (tdoa_stream_phat.hip) share,
+// one definition each, collective over one 256-thread workgroup:
+//
+//   phat_front_end  DC floor mean, prep_word, z[n] = x[2n] + i x[2n+1] zero
+//                   padded into the FFT buffer
+//   fft_inplace     the in-place Stockham FFT_N
+//   phat_split      real-FFT split to X[0..N] (slot 0 packs X[0], X[N]), raw
+//                   or as the PHAT unit spectrum U = X / sqrt(|X|^2 + e2)
+//   phat_fold       Hermitian fold and inverse pre-twiddle of bins k, N - k
+//   phat_lags       lags -S..S of the inverse, times 1 / 2N
+//   wave_first_max  first maximum of a score row, NaN clamp and tie rule
+//   prior_weighted  the lag prior on a lane's two candidates
+//
+// so a streamed frame's scores are the two-pass route's by construction.
+// Internal linkage per TU.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <climits>
+
+#include "tdoa_prep.h"  // prep_word, sum_word
 
 namespace {
 
@@ -97,18 +113,138 @@ __device__ void fft_inplace(f2 *buf, int n, const float *__restrict__ tw)
     }
 }
 
-__device__ __forceinline__ uint32_t prep_word(uint32_t v, uint32_t off16, uint32_t wv)
+// Integer front end of one mic row x (N int16 samples as N/2 packed words, in
+// global memory or LDS): floor-mean DC removal (rolling_buffer.c:64-66), << 8
+// wrap and Q15 window (buffer.c:13-16, buffer.c:4-11), then z[n] = x[2n] +
+// i x[2n+1] into buf[0..N/2) and zeros into buf[N/2..N).  red: [TPB/64] in LDS.
+// Ends with a barrier: buf is ready for fft_inplace.
+__device__ __forceinline__ void phat_front_end(const uint32_t *x, const uint32_t *win, int N, int log2N, int *red,
+                                               f2 *buf)
 {
-    // (int16)(x - off), then <<= 8 keeps the low byte, then (x * W) >> 15
-    uint32_t r = 0;
+    const int NW = N / 2, tid = threadIdx.x;
+    int s = 0;
+    for (int w = tid; w < NW; w += TPB)
+        s += sum_word(x[w]);
 #pragma unroll
-    for (int h = 0; h < 2; h++) {
-        const uint32_t x = (v >> (16 * h)) & 0xFFFFu;
-        const int32_t w = (int32_t)(int16_t)((wv >> (16 * h)) & 0xFFFFu);
-        const int32_t z = (int32_t)(int16_t)(uint16_t)((((x - off16) & 0xFFFFu) << 8) & 0xFFFFu);
-        r |= ((uint32_t)((z * w) >> 15) & 0xFFFFu) << (16 * h);
+    for (int o = 32; o >= 1; o >>= 1)
+        s += __shfl_xor(s, o, 64);
+    if ((tid & 63) == 0)
+        red[tid >> 6] = s;
+    __syncthreads();
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < TPB / 64; w++)
+        tot += red[w];
+    const uint32_t off16 = (uint32_t)(tot >> log2N) & 0xFFFFu;  // floor mean, (int16)
+    for (int w = tid; w < N; w += TPB) {
+        f2 z = f2{0.0f, 0.0f};
+        if (w < NW) {
+            const uint32_t p = prep_word(x[w], off16, win[w]);
+            z = f2{(float)(int16_t)(p & 0xFFFFu), (float)(int16_t)(p >> 16)};
+        }
+        buf[w] = z;
     }
-    return r;
+    __syncthreads();
+}
+
+// a bin as the split stores it: raw, or divided by sqrt(|X|^2 + e2) (UNIT)
+template <bool UNIT>
+__device__ __forceinline__ float phat_bin(float x, float e2)
+{
+    return UNIT ? x * __builtin_amdgcn_rsqf(x * x + e2) : x;
+}
+template <bool UNIT>
+__device__ __forceinline__ f2 phat_bin(f2 x, float e2)
+{
+    if (UNIT)
+        x *= __builtin_amdgcn_rsqf(x.x * x.x + x.y * x.y + e2);
+    return x;
+}
+
+// Real-FFT split of buf = FFT_N(z) to the 2N-point spectrum of the row:
+// X[k] = (Z[k] + Z*[N-k])/2 - i/2 W_2N^k (Z[k] - Z*[N-k]), N complex to o (slot
+// 0 packs the two real bins X[0], X[N]).  tw2 = W_2N^k.  No barrier at the end.
+template <bool UNIT>
+__device__ __forceinline__ void phat_split(const f2 *buf, f2 *o, int N, const float *__restrict__ tw2, float e2)
+{
+    for (int k = threadIdx.x; k <= N / 2; k += TPB) {
+        const int kn = (N - k) & (N - 1);
+        const f2 a = buf[k], b = buf[kn];
+        if (k == 0) {
+            o[0] = f2{phat_bin<UNIT>(a.x + a.y, e2), phat_bin<UNIT>(a.x - a.y, e2)};  // X[0], X[N]: both real
+            continue;
+        }
+        const f2 w2k = ldtw(tw2, k), w2n = ldtw(tw2, N - k);
+        const f2 e = a + conj2(b), d = cmul(w2k, a - conj2(b));
+        o[k] = phat_bin<UNIT>(0.5f * f2{e.x + d.y, e.y - d.x}, e2);
+        if (k != N / 2) {
+            const f2 ee = b + conj2(a), dd = cmul(w2n, b - conj2(a));
+            o[kn] = phat_bin<UNIT>(0.5f * f2{ee.x + dd.y, ee.y - dd.x}, e2);
+        }
+    }
+}
+
+// Hermitian fold and inverse pre-twiddle of the cross spectrum's bins k and
+// N - k (k <= N/2): Y[k] = (R[k] + R*[N-k]) + i (R[k] - R*[N-k]) conj(W_2N^k)
+// into buf[k], and its mirror into buf[N-k]
+__device__ __forceinline__ void phat_fold(f2 *buf, int N, int k, f2 Rk, f2 Rn, const float *__restrict__ tw2)
+{
+    const int kn = (N - k) & (N - 1);
+    const f2 w2k = ldtw(tw2, k), w2n = ldtw(tw2, N - k);
+    buf[k] = (Rk + conj2(Rn)) + mul_i(cmul(Rk - conj2(Rn), conj2(w2k)));
+    if (k != 0 && k != N / 2)
+        buf[kn] = (Rn + conj2(Rk)) + mul_i(cmul(Rn - conj2(Rk), conj2(w2n)));
+}
+
+// Lags -S..S of buf = inverse FFT_N(Y) into sc[0..K): r[s] = y / 2N at s mod
+// 2N, r[2u] = Re y[u], r[2u+1] = Im y[u].  Ends with a barrier.
+__device__ __forceinline__ void phat_lags(const f2 *buf, float *sc, int N, int K, int S)
+{
+    const float invL = 1.0f / (float)(2 * N);
+    for (int i = threadIdx.x; i < K; i += TPB) {
+        const int s = i - S;
+        const int m = s < 0 ? s + 2 * N : s;
+        const f2 y = buf[m >> 1];
+        sc[i] = ((m & 1) ? y.y : y.x) * invL;
+    }
+    __syncthreads();
+}
+
+// first maximum of row[0..K) (K <= 127) over one wave: two candidates per lane
+// in ascending order (v1 = row[lane], v2 = row[lane + 64], -inf past K),
+// strict '>' keeps the first; the same index in every lane
+__device__ __forceinline__ int wave_first_max(float v1, float v2, int lane, int K)
+{
+    const int k1 = lane, k2 = lane + 64;
+    float bv = v1;
+    int bk = k1 < K ? k1 : INT_MAX;
+    if (k2 < K && (v2 > bv || bk == INT_MAX)) {
+        bv = v2;
+        bk = k2;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int ok = __shfl_xor(bk, o, 64);
+        if (ov > bv || (ov == bv && ok < bk) || (bk == INT_MAX && ok != INT_MAX)) {
+            bv = ov;
+            bk = ok;
+        }
+    }
+    bk = __shfl(bk, 0, 64);
+    return bk < 0 ? 0 : (bk >= K ? K - 1 : bk);  // NaN scores: keep the index in range
+}
+
+// the lag prior on a lane's two candidates (correlations.c:20-33 on float
+// scores): w[k] = v[k] * prior[|k - bk|] for k = lane, lane + 64 below K
+__device__ __forceinline__ void prior_weighted(float *w, const float *__restrict__ prior, float v1, float v2,
+                                               int lane, int K, int bk)
+{
+    const int k1 = lane, k2 = lane + 64;
+    if (k1 < K)
+        w[k1] = v1 * prior[k1 > bk ? k1 - bk : bk - k1];
+    if (k2 < K)
+        w[k2] = v2 * prior[k2 > bk ? k2 - bk : bk - k2];
 }
 
 }  // namespace

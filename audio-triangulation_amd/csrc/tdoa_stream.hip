@@ -693,13 +693,6 @@ __global__ void __launch_bounds__(TPB) k_stream_update(tdoa_stream_params sp, td
     }
 }
 
-int fail_hip(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return tdoa_set_error(-2, buf);
-}
-
 }  // namespace
 
 size_t tdoa_stream_trigger_lds(int M, int N, int H)
@@ -756,7 +749,7 @@ int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *st
             launch_trigger_m<16>(sp, S, st);
         *by_id = true;  // firing streams listed only: DIRECT reads their frames from the ring
         hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : fail_hip(e, "k_stream_trigger_p launch");
+        return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger_p launch");
     }
     *by_id = false;  // frames in compact slots
     if (sp.H > TPB * MAX_CAND)
@@ -766,7 +759,7 @@ int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *st
         return tdoa_set_error(-1, "stream: (frame_len + hop) x mics exceeds the LDS budget");
     hipLaunchKernelGGL(k_stream_trigger, dim3((unsigned)S), dim3(TPB), lds, st, sp);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip(e, "k_stream_trigger launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger launch");
 }
 
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,
@@ -777,5 +770,5 @@ int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &
     hipLaunchKernelGGL(k_stream_update, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TPB), lds, (hipStream_t)stream, sp,
                        kp, out, (int)S);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip(e, "k_stream_update launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_update launch");
 }

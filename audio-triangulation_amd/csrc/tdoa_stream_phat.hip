@@ -18,10 +18,11 @@
 //                  first maxima and the grid solve on the EMA scores over the
 //                  distinct lag tuples (float L, first tuple on ties).
 //
-// The FFT, the split and the front end are tdoa_phat_split.hip's (one copy,
-// tdoa_phat_lds.h); the unit spectra, the pre-twiddle and the argmax are
-// k_phat_spectra's / k_phat_pairs_w's expressions, so a frame's scores are
-// those of the two-pass route.  Samples stay in int16 units (eps x 2^30).
+// Every stage from the front end to the lag prior is a function of
+// tdoa_phat_lds.h, the one k_phat_spectra and k_phat_pairs call, so a frame's
+// scores are those of the two-pass route.  What is this file's own: the slot
+// staging, the gate and the record, the float EMA, the EMA rows' maxima, the
+// grid scan and the diagnostic stamps.  Samples stay in int16 units (eps x 2^30).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -72,36 +73,12 @@ __device__ __forceinline__ float ema_step(float est, float fresh, float dec)
     return est + delta;
 }
 
-// first maximum of row[0..K) (K <= 127) over one wave: two candidates per lane
-// in ascending order, strict '>' keeps the first; the same index in every lane
-__device__ __forceinline__ int wave_first_max(float v1, float v2, int lane, int K)
-{
-    const int k1 = lane, k2 = lane + 64;
-    float bv = v1;
-    int bk = k1 < K ? k1 : INT_MAX;
-    if (k2 < K && (v2 > bv || bk == INT_MAX)) {
-        bv = v2;
-        bk = k2;
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int ok = __shfl_xor(bk, o, 64);
-        if (ov > bv || (ov == bv && ok < bk) || (bk == INT_MAX && ok != INT_MAX)) {
-            bv = ov;
-            bk = ok;
-        }
-    }
-    bk = __shfl(bk, 0, 64);
-    return bk < 0 ? 0 : (bk >= K ? K - 1 : bk);  // NaN scores: keep the index in range
-}
-
 __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa_kparams kp, tdoa_stream_kout out,
                                                      float *__restrict__ est_all, float *__restrict__ max_Lf,
                                                      int nstreams, int by_id, float e2)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int N = kp.N, NW = N / 2, M = kp.M, P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
+    const int N = kp.N, M = kp.M, P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, nwaves = TPB / 64;
     f2 *U = (f2 *)smem;                // [M][N] unit spectra (slot 0 = bins 0 and N); a mic's raw samples before
     f2 *buf = U + (size_t)M * N;       // [N] FFT work buffer
@@ -162,56 +139,10 @@ __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa
 
         // ---- per mic: front end, FFT_N, split, unit spectrum
         for (int m = 0; m < M; m++) {
-            const uint32_t *x = reinterpret_cast<const uint32_t *>(U + (size_t)m * N);
-            int sum = 0;
-            for (int w = tid; w < NW; w += TPB) {
-                const uint32_t v = x[w];
-                sum += (int)(int16_t)(v & 0xFFFFu) + (int)(int16_t)(v >> 16);
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1)
-                sum += __shfl_xor(sum, o, 64);
-            if (lane == 0)
-                red[wave] = sum;
-            __syncthreads();
-            int tot = 0;
-#pragma unroll
-            for (int w = 0; w < TPB / 64; w++)
-                tot += red[w];
-            const uint32_t off16 = (uint32_t)(tot >> kp.log2N) & 0xFFFFu;  // floor mean, (int16)
-            for (int w = tid; w < N; w += TPB) {
-                f2 z = f2{0.0f, 0.0f};
-                if (w < NW) {
-                    const uint32_t p = prep_word(x[w], off16, win[w]);
-                    z = f2{(float)(int16_t)(p & 0xFFFFu), (float)(int16_t)(p >> 16)};
-                }
-                buf[w] = z;
-            }
-            __syncthreads();
+            f2 *row = U + (size_t)m * N;
+            phat_front_end(reinterpret_cast<const uint32_t *>(row), win, N, kp.log2N, red, buf);
             fft_inplace<false>(buf, N, kp.tw);
-
-            // X[k] = (Z[k] + Z*[N-k])/2 - i/2 W_2N^k (Z[k] - Z*[N-k]), then U = X / sqrt(|X|^2 + e2)
-            f2 *o = U + (size_t)m * N;
-            for (int k = tid; k <= N / 2; k += TPB) {
-                const int kn = (N - k) & (N - 1);
-                const f2 a = buf[k], b = buf[kn];
-                if (k == 0) {  // X[0], X[N]: both real
-                    const float x0 = a.x + a.y, xn = a.x - a.y;
-                    o[0] = f2{x0 * __builtin_amdgcn_rsqf(x0 * x0 + e2), xn * __builtin_amdgcn_rsqf(xn * xn + e2)};
-                    continue;
-                }
-                const f2 w2k = ldtw(kp.tw2, k), w2n = ldtw(kp.tw2, N - k);
-                const f2 e = a + conj2(b), d = cmul(w2k, a - conj2(b));
-                f2 xk = 0.5f * f2{e.x + d.y, e.y - d.x};
-                xk *= __builtin_amdgcn_rsqf(xk.x * xk.x + xk.y * xk.y + e2);
-                o[k] = xk;
-                if (k != N / 2) {
-                    const f2 ee = b + conj2(a), dd = cmul(w2n, b - conj2(a));
-                    f2 xn = 0.5f * f2{ee.x + dd.y, ee.y - dd.x};
-                    xn *= __builtin_amdgcn_rsqf(xn.x * xn.x + xn.y * xn.y + e2);
-                    o[kn] = xn;
-                }
-            }
+            phat_split<true>(buf, row, N, kp.tw2, e2);  // U = X / sqrt(|X|^2 + e2)
             __syncthreads();  // buf and red are free for the next mic
         }
 
@@ -221,8 +152,7 @@ __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa
         for (int p = 0; p < P; p++) {
             const f2 *Ui = U + (size_t)kp.pair_i[p] * N;
             const f2 *Uj = U + (size_t)kp.pair_j[p] * N;
-            // R = conj(U_i) U_j;  Y[k] = (R[k] + R*[N-k]) + i (R[k] - R*[N-k]) conj(W_2N^k)
-            for (int k = tid; k <= N / 2; k += TPB) {
+            for (int k = tid; k <= N / 2; k += TPB) {  // R = conj(U_i) U_j
                 const int kn = (N - k) & (N - 1);
                 f2 ik = Ui[k], in = Ui[kn], jk = Uj[k], jn = Uj[kn];
                 if (k == 0) {  // slot 0 = (U[0], U[N]), both real
@@ -236,31 +166,16 @@ __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa
                     Rk = bw[k] * Rk;
                     Rn = bw[N - k] * Rn;
                 }
-                const f2 w2k = ldtw(kp.tw2, k), w2n = ldtw(kp.tw2, N - k);
-                buf[k] = (Rk + conj2(Rn)) + mul_i(cmul(Rk - conj2(Rn), conj2(w2k)));
-                if (k != 0 && k != N / 2)
-                    buf[kn] = (Rn + conj2(Rk)) + mul_i(cmul(Rn - conj2(Rk), conj2(w2n)));
+                phat_fold(buf, N, k, Rk, Rn, kp.tw2);
             }
             __syncthreads();
             fft_inplace<true>(buf, N, kp.tw);
-
-            // r[s] = y / 2N at s mod 2N:  r[2u] = Re y[u], r[2u+1] = Im y[u]
-            const float invL = 1.0f / (float)(2 * N);
-            for (int i = tid; i < K; i += TPB) {
-                const int sh = i - S;
-                const int mm = sh < 0 ? sh + 2 * N : sh;
-                const f2 y = buf[mm >> 1];
-                sc[i] = ((mm & 1) ? y.y : y.x) * invL;
-            }
-            __syncthreads();
+            phat_lags(buf, sc, N, K, S);
             if (tid < 64) {
                 const int k1 = lane, k2 = lane + 64;
                 const float v1 = k1 < K ? sc[k1] : -INFINITY, v2 = k2 < K ? sc[k2] : -INFINITY;
                 const int bk = wave_first_max(v1, v2, lane, K);
-                if (k1 < K)
-                    Wf[p * K + k1] = v1 * kp.prior[k1 > bk ? k1 - bk : bk - k1];
-                if (k2 < K)
-                    Wf[p * K + k2] = v2 * kp.prior[k2 > bk ? k2 - bk : bk - k2];
+                prior_weighted(Wf + p * K, kp.prior, v1, v2, lane, K, bk);
                 if (lane == 0)
                     lag_s[p] = bk - S;
             }
@@ -402,13 +317,6 @@ __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa
         atomicAdd(reinterpret_cast<unsigned long long *>(sp.stats + 1), (unsigned long long)ngated);
 }
 
-int fail_hip(hipError_t e, const char *what)
-{
-    char buf[256];
-    snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
-    return tdoa_set_error(-2, buf);
-}
-
 }  // namespace
 
 #ifdef TDOA_DIAG
@@ -433,8 +341,7 @@ static constexpr size_t LDS_BUDGET = 160 * 1024 - 1024;
 
 bool tdoa_stream_phat_fits(const tdoa_kparams &kp)
 {
-    return kp.N >= 256 && kp.N <= 4096 && !(kp.N & (kp.N - 1)) && kp.K <= 127 &&
-           tdoa_stream_phat_lds(kp) <= LDS_BUDGET;
+    return tdoa_phat_lds_shape(kp.N, kp.K) && tdoa_stream_phat_lds(kp) <= LDS_BUDGET;
 }
 
 int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap)
@@ -454,14 +361,9 @@ int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp
 {
     if (!tdoa_stream_phat_fits(kp))
         return tdoa_set_error(-1, "stream GCC_PHAT: shape exceeds the LDS budget");
-    // the per-mic floor as tdoa_launch_gcc_phat passes it to k_phat_spectra's
-    // consumers: a normal float, in int16 units
-    float eps = phat_eps;
-    if (!(eps >= 1e-30f))
-        eps = 1e-30f;
     hipLaunchKernelGGL(k_stream_phat, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TPB), tdoa_stream_phat_lds(kp),
                        (hipStream_t)stream, sp, kp, out, est, max_Lf, (int)S, by_id ? 1 : 0,
-                       eps * 1073741824.0f /* 2^30: int16 units */);
+                       tdoa_phat_floor_int16(phat_eps));
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail_hip(e, "k_stream_phat launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_phat launch");
 }

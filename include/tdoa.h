@@ -231,7 +231,7 @@ int tdoa_peaks(tdoa_ctx *ctx, const void *scores, int is_float, int64_t B,
  * (min_rel of tdoa_peaks is relative and unaffected).
  *
  * While a table is set, a tdoa_localize_batch of the context runs the two-pass
- * kernels (k_phat_spectra, then k_phat_pairs_w) for every shape, through a
+ * kernels (k_phat_spectra, then k_phat_pairs<true>) for every shape, through a
  * spectrum scratch of the context: tdoa_batch_kernel names the first of them
  * and tdoa_batch_grid_fused returns 0 -- one stream per context while a call
  * is in flight.  Without a table (never set, or cleared with NULL) the context

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Price the band-limited GCC-PHAT route (tdoa_set_bin_weights: k_phat_spectra,
-then k_phat_pairs_w) against the route a context takes without a table.
+then k_phat_pairs<true>) against the route a context takes without a table.
 
 One context per shape, its variants alternated round by round in one process
 (none / all-ones table / 1-6 kHz band), each round: set the table, two warm

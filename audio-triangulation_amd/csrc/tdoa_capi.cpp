@@ -45,7 +45,7 @@ struct tdoa_ctx {
     tdoa_devmem rscratch, cscratch, tscratch;
     tdoa_devmem pscratch;  // tdoa_peaks: [B][Kp][P] lag tuples when only the refinement reads them
     // GCC_PHAT spectrum scratch (TDOA_SPEC_BYTES) of the two-pass shapes (M > 3
-    // or N > 2048) and, on demand, of a band-limited context
+    // or N > 2048) and, on demand, of a band-limited or 16-bit (PCM16) context
     tdoa_devmem spec;
     // band-limited GCC_PHAT (tdoa_set_bin_weights): the table in force (empty:
     // none) and its device copy, [N + 1] floats, kept once allocated
@@ -640,6 +640,38 @@ extern "C" int tdoa_get_bin_weights(const tdoa_ctx *c, float *w)
     return TDOA_OK;
 }
 
+
+// ------------------------------------------------------- 16-bit PCM input
+extern "C" int tdoa_set_sample_format(tdoa_ctx *ctx, int format)
+{
+    if (!ctx)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_set_sample_format: NULL ctx");
+    if (format != TDOA_SAMPLES_ADC8 && format != TDOA_SAMPLES_PCM16)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_set_sample_format: unknown format %d", format);
+    if (format == TDOA_SAMPLES_PCM16) {
+        if (ctx->t.cfg.engine != TDOA_ENGINE_GCC_PHAT)
+            return tdoa_fail(TDOA_ERR_INVALID, "tdoa_set_sample_format: PCM16 needs a GCC_PHAT context");
+        // a shape without a fused PCM16 kernel takes the two-pass route: a
+        // context whose 8-bit kernel is fused gets the spectrum scratch here
+        const bool fused = tdoa_phat1024_fits(ctx->kp) ||
+                           (tdoa_phat_r16_fits(ctx->kp.M, ctx->kp.N, ctx->kp.S) && frame16_shape(ctx->kp));
+        if (!fused && !ctx->spec) {
+            HIP_TRY(hipSetDevice(ctx->device));
+            if (ctx->spec.alloc(TDOA_SPEC_BYTES) != hipSuccess)
+                return tdoa_fail(TDOA_ERR_NOMEM, "GCC_PHAT spectrum scratch of %zu bytes", TDOA_SPEC_BYTES);
+        }
+    }
+    ctx->kp.pcm16 = format == TDOA_SAMPLES_PCM16 ? 1 : 0;
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_get_sample_format(const tdoa_ctx *ctx, int *format)
+{
+    if (!ctx || !format)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_get_sample_format: NULL argument");
+    *format = ctx->kp.pcm16 ? TDOA_SAMPLES_PCM16 : TDOA_SAMPLES_ADC8;
+    return TDOA_OK;
+}
 
 extern "C" const char *tdoa_batch_kernel(const tdoa_ctx *ctx)
 {

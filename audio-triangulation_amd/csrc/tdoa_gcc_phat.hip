@@ -687,13 +687,21 @@ static bool use_w64(const tdoa_kparams &kp)
 
 // The one dispatch decision of tdoa_launch_gcc_phat, shared with
 // tdoa_gcc_phat_kernel_name so the reported kernel is the launched one.
-enum class PhatRoute { BAND, W64, P1K_LEAN, R16, SPLIT, FUSED_1024, GENERIC };
+enum class PhatRoute { BAND, W64, P1K_LEAN, R16, SPLIT, FUSED_1024, GENERIC, P1K_PCM16, F16_PCM16 };
 static PhatRoute phat_route(const tdoa_kparams &kp)
 {
     // a weight table (tdoa_set_bin_weights): every shape takes the two-pass
     // kernels with the weighted pass 2 (k_phat_spectra, k_phat_pairs<true>)
     if (kp.bin_w)
         return PhatRoute::BAND;
+    // 16-bit samples (tdoa_set_sample_format): the fused PCM16 kernels for the
+    // product's shapes -- no A/B switch picks another -- and the two-pass
+    // route with the PCM16 pass 1 for every other shape
+    if (kp.pcm16) {
+        if (tdoa_phat1024_fits(kp))
+            return PhatRoute::P1K_PCM16;
+        return tdoa_phat_r16_fits(kp.M, kp.N, kp.S) && frame16_shape(kp) ? PhatRoute::F16_PCM16 : PhatRoute::SPLIT;
+    }
     if (use_w64(kp))
         return PhatRoute::W64;
     if (tdoa_phat1024_fits(kp))
@@ -711,7 +719,11 @@ const char *tdoa_gcc_phat_kernel_name(const tdoa_kparams &kp)
 {
     switch (phat_route(kp)) {
     case PhatRoute::BAND:
-        return "k_phat_spectra";
+        return kp.pcm16 ? "k_phat_spectra_pcm16" : "k_phat_spectra";
+    case PhatRoute::P1K_PCM16:
+        return "k_p1k_pcm16";
+    case PhatRoute::F16_PCM16:
+        return "k_f16_pcm16";
     case PhatRoute::W64:
         return "k_p1k_w64";
     case PhatRoute::P1K_LEAN:
@@ -719,7 +731,7 @@ const char *tdoa_gcc_phat_kernel_name(const tdoa_kparams &kp)
     case PhatRoute::R16:
         return frame16_shape(kp) ? frame16_kernel_name(kp) : "k_spec16";
     case PhatRoute::SPLIT:
-        return "k_phat_spectra";
+        return kp.pcm16 ? "k_phat_spectra_pcm16" : "k_phat_spectra";
     case PhatRoute::FUSED_1024:
         return "k_gcc_phat_1024";
     case PhatRoute::GENERIC:
@@ -736,13 +748,18 @@ bool tdoa_gcc_phat_grid_in_kernel(const tdoa_kparams &kp)
         return false;  // weighted scores through the context's scratch, then tdoa_launch_grid
     if (r == PhatRoute::R16)
         return tdoa_frame16_fused_grid(kp);
+    if (r == PhatRoute::P1K_PCM16)
+        return true;
+    if (r == PhatRoute::F16_PCM16 || r == PhatRoute::SPLIT)
+        return false;  // k_grid_bb / k_grid follows
     return !tdoa_gcc_phat_needs_split(kp.M, kp.N) && tdoa_gcc_phat_fused_grid(kp);
 }
 
 // the launch writes the least-squares peak scores (kout.peak3) itself
 bool tdoa_gcc_phat_peak3(const tdoa_kparams &kp)
 {
-    return phat_route(kp) != PhatRoute::BAND && tdoa_phat_r16_peak3(kp);
+    const PhatRoute r = phat_route(kp);
+    return (r == PhatRoute::R16 || r == PhatRoute::F16_PCM16) && tdoa_phat_r16_peak3(kp);
 }
 
 // the N = 1024, M = 3 kernels (k_p1k_lean, k_gcc_phat_1024) solve the grid
@@ -769,9 +786,9 @@ int tdoa_launch_gcc_phat(const tdoa_kparams &kp, const tdoa_kout &out, const int
     if (route == PhatRoute::W64)
         return tdoa_launch_p1k_w64(kp, out, frames, B, phat_eps, stream);
 #endif
-    if (route == PhatRoute::P1K_LEAN)
+    if (route == PhatRoute::P1K_LEAN || route == PhatRoute::P1K_PCM16)
         return tdoa_launch_phat1024(kp, out, frames, B, phat_eps, stream);
-    if (route == PhatRoute::R16)
+    if (route == PhatRoute::R16 || route == PhatRoute::F16_PCM16)
         return tdoa_launch_phat_r16(kp, out, frames, B, phat_eps, spec_scratch, spec_bytes, stream);
     if (route == PhatRoute::SPLIT || route == PhatRoute::BAND)
         return tdoa_launch_gcc_phat_split(kp, out, frames, B, tdoa_phat_floor_int16(phat_eps), spec_scratch,

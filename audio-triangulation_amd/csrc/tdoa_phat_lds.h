@@ -2,7 +2,7 @@
 // (tdoa_phat_split.hip) and the streaming kernel (tdoa_stream_phat.hip) share,
 // one definition each, collective over one 256-thread workgroup:
 //
-//   phat_front_end  DC floor mean, prep_word, z[n] = x[2n] + i x[2n+1] zero
+//   phat_front_end  DC floor mean, prep_word (or pcm16_sample), z[n] = x[2n] + i x[2n+1] zero
 //                   padded into the FFT buffer
 //   fft_inplace     the in-place Stockham FFT_N
 //   phat_split      real-FFT split to X[0..N] (slot 0 packs X[0], X[N]), raw
@@ -21,7 +21,7 @@
 
 #include <climits>
 
-#include "tdoa_prep.h"  // prep_word, sum_word
+#include "tdoa_prep.h"  // prep_word, pcm16_sample, sum_word
 
 namespace {
 
@@ -118,6 +118,11 @@ __device__ void fft_inplace(f2 *buf, int n, const float *__restrict__ tw)
 // wrap and Q15 window (buffer.c:13-16, buffer.c:4-11), then z[n] = x[2n] +
 // i x[2n+1] into buf[0..N/2) and zeros into buf[N/2..N).  red: [TPB/64] in LDS.
 // Ends with a barrier: buf is ready for fft_inplace.
+// PCM16 (TDOA_SAMPLES_PCM16, include/tdoa.h): the same DC reduction, then
+// y = x - off in int32 without the wrap (|y| <= 65535) and s = (y W) >> 15
+// (|y W| < 2^31; |s| <= 65535, exact in fp32) straight to f2 -- no packed int16
+// intermediate holds 17 bits.
+template <bool PCM16 = false>
 __device__ __forceinline__ void phat_front_end(const uint32_t *x, const uint32_t *win, int N, int log2N, int *red,
                                                f2 *buf)
 {
@@ -135,12 +140,19 @@ __device__ __forceinline__ void phat_front_end(const uint32_t *x, const uint32_t
 #pragma unroll
     for (int w = 0; w < TPB / 64; w++)
         tot += red[w];
-    const uint32_t off16 = (uint32_t)(tot >> log2N) & 0xFFFFu;  // floor mean, (int16)
+    const int off = tot >> log2N;                          // floor mean
+    const uint32_t off16 = (uint32_t)off & 0xFFFFu;        // ... as (int16)
     for (int w = tid; w < N; w += TPB) {
         f2 z = f2{0.0f, 0.0f};
         if (w < NW) {
-            const uint32_t p = prep_word(x[w], off16, win[w]);
-            z = f2{(float)(int16_t)(p & 0xFFFFu), (float)(int16_t)(p >> 16)};
+            if constexpr (PCM16) {
+                const uint32_t v = x[w], wv = win[w];
+                z = f2{(float)pcm16_sample((int16_t)(v & 0xFFFFu), off, (int16_t)(wv & 0xFFFFu)),
+                       (float)pcm16_sample((int16_t)(v >> 16), off, (int16_t)(wv >> 16))};
+            } else {
+                const uint32_t p = prep_word(x[w], off16, win[w]);
+                z = f2{(float)(int16_t)(p & 0xFFFFu), (float)(int16_t)(p >> 16)};
+            }
         }
         buf[w] = z;
     }

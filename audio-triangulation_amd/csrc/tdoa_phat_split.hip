@@ -4,7 +4,8 @@
 // split in two passes over chunks of frames:
 //
 //   k_phat_spectra  one workgroup per (frame, mic) row: the integer front end
-//                   (rolling_buffer.c:64-66, buffer.c:13-16, buffer.c:4-11),
+//                   (rolling_buffer.c:64-66, buffer.c:13-16, buffer.c:4-11;
+//                   k_phat_spectra_pcm16: the 16-bit one, TDOA_SAMPLES_PCM16),
 //                   complex FFT_N of z[n] = x[2n] + i x[2n+1] in LDS and the
 //                   split to X[0..N] of the real FFT_2N, stored N complex per
 //                   row (slot 0 packs the two real bins X[0], X[N]) to a
@@ -32,20 +33,25 @@
 namespace {
 
 // ---------------------------------------------------------------- pass 1
-__global__ void __launch_bounds__(TPB) k_phat_spectra(tdoa_kparams kp,
-                                                      const int16_t *__restrict__ frames,
-                                                      int64_t row0, f2 *__restrict__ spec)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    f2 *buf = (f2 *)smem;  // [N]
-    __shared__ int red[TPB / 64];
-    const int N = kp.N;
-    const int64_t row = row0 + blockIdx.x;
-    phat_front_end(reinterpret_cast<const uint32_t *>(frames + row * (int64_t)N),
-                   reinterpret_cast<const uint32_t *>(kp.window), N, kp.log2N, red, buf);
-    fft_inplace<false>(buf, N, kp.tw);
-    phat_split<false>(buf, spec + (size_t)blockIdx.x * N, N, kp.tw2, 0.0f);
-}
+// one definition for both sample formats: k_phat_spectra (8-bit ADC front end)
+// and k_phat_spectra_pcm16 (TDOA_SAMPLES_PCM16) differ in phat_front_end alone
+#define PHAT_SPECTRA_KERNEL(NAME, PCM16)                                                                      \
+    __global__ void __launch_bounds__(TPB) NAME(tdoa_kparams kp, const int16_t *__restrict__ frames,         \
+                                                int64_t row0, f2 *__restrict__ spec)                          \
+    {                                                                                                         \
+        extern __shared__ __attribute__((aligned(16))) char smem[];                                           \
+        f2 *buf = (f2 *)smem; /* [N] */                                                                       \
+        __shared__ int red[TPB / 64];                                                                         \
+        const int N = kp.N;                                                                                   \
+        const int64_t row = row0 + blockIdx.x;                                                                \
+        phat_front_end<PCM16>(reinterpret_cast<const uint32_t *>(frames + row * (int64_t)N),                  \
+                              reinterpret_cast<const uint32_t *>(kp.window), N, kp.log2N, red, buf);          \
+        fft_inplace<false>(buf, N, kp.tw);                                                                    \
+        phat_split<false>(buf, spec + (size_t)blockIdx.x * N, N, kp.tw2, 0.0f);                               \
+    }
+PHAT_SPECTRA_KERNEL(k_phat_spectra, false)
+PHAT_SPECTRA_KERNEL(k_phat_spectra_pcm16, true)
+#undef PHAT_SPECTRA_KERNEL
 
 // ---------------------------------------------------------------- pass 2
 __device__ __forceinline__ void load_bins(const f2 *X, int k, int kn, f2 &xk, f2 &xn)
@@ -198,8 +204,8 @@ int tdoa_launch_gcc_phat_split(const tdoa_kparams &kp, const tdoa_kout &out,
         const int64_t nf = (B - c0) < chunk ? (B - c0) : chunk;
         if (nf * P > INT_MAX)
             return tdoa_set_error(-1, "GCC_PHAT: chunk too large for one launch");
-        hipLaunchKernelGGL(k_phat_spectra, dim3((unsigned)(nf * M)), dim3(TPB), lds1, st, kp, frames,
-                           c0 * M, (f2 *)scratch);
+        hipLaunchKernelGGL(kp.pcm16 ? k_phat_spectra_pcm16 : k_phat_spectra, dim3((unsigned)(nf * M)), dim3(TPB),
+                           lds1, st, kp, frames, c0 * M, (f2 *)scratch);
         if (kp.bin_w)
             hipLaunchKernelGGL(k_phat_pairs<true>, dim3((unsigned)(nf * P)), dim3(TPB), lds2, st, kp, out,
                                (const f2 *)scratch, c0, nf * P, eps_int16);

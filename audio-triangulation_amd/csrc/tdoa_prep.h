@@ -24,6 +24,14 @@ __device__ __forceinline__ uint32_t prep_word(uint32_t v, uint32_t off16, uint32
     return prep_sample(v & 0xFFFFu, off16, w0) | (prep_sample(v >> 16, off16, w1) << 16);
 }
 
+// TDOA_SAMPLES_PCM16 (include/tdoa.h) for one sample: y = x - off without the
+// wrap, s = (y W) >> 15 as an arithmetic shift (floor).  |y| <= 65535 and
+// 0 <= W <= 32767 fit 24 bits and |y W| < 2^31: one v_mul_i32_i24
+__device__ __forceinline__ int32_t pcm16_sample(int32_t x, int32_t off, int32_t w)
+{
+    return __mul24(x - off, w) >> 15;
+}
+
 __device__ __forceinline__ int sum_word(uint32_t v)
 {
     return (int)(int16_t)(v & 0xFFFFu) + (int)(int16_t)(v >> 16);

@@ -96,6 +96,12 @@ struct tdoa_kparams {
     // capture ring's values: half the bytes of int16 copies), widened to int16
     // when staged
     int32_t frames_u8;
+    // sample format of a GCC_PHAT batch (tdoa_set_sample_format): 0 the 8-bit
+    // ADC front end, 1 full-range int16 (TDOA_SAMPLES_PCM16).  It picks the
+    // launch's kernels on the host; no kernel reads it.  It fills the four
+    // bytes of padding ahead of mic_xy, so no other field moves and every
+    // kernel's argument offsets stay as they were
+    int32_t pcm16;
     // least-squares refinement (tdoa_ls.hip)
     const float *mic_xy;       // [M][2] metres
     float fs, c, height;

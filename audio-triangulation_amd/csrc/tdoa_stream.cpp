@@ -149,6 +149,9 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     const bool phat = engine == TDOA_ENGINE_GCC_PHAT;
     const tdoa_kparams &kp = *tdoa_ctx_kparams(ctx);
     const int M = kp.M, N = kp.N, P = kp.P, K = kp.K;
+    if (kp.pcm16)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: the capture ring is 8-bit; the context's sample "
+                                           "format is PCM16 (tdoa_set_sample_format)");
     if (phat && !tdoa_stream_phat_fits(kp))
         return tdoa_fail(TDOA_ERR_INVALID,
                          "tdoa_stream_create: GCC_PHAT with %d mics x frame_len %d needs %zu bytes of LDS per "

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("TDOA_LIB") or os.path.join(HERE, "libtdoa.so")
 ENGINE_DIRECT = 0
 ENGINE_GCC_PHAT = 1
 ENGINES = {"direct": ENGINE_DIRECT, "gcc_phat": ENGINE_GCC_PHAT}
+SAMPLE_FORMATS = {"adc8": 0, "pcm16": 1}  # tdoa_sample_format
 
 STATUS = {0: "TDOA_OK", -1: "TDOA_ERR_INVALID", -2: "TDOA_ERR_HIP",
           -3: "TDOA_ERR_NO_DEVICE", -4: "TDOA_ERR_NOMEM"}
@@ -31,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
+    "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
     "microphones_init", "rolling_buffer_init", "rolling_buffer_push",
     "rolling_buffer_write_out", "rolling_buffer_get_incoming_power",
@@ -163,6 +165,8 @@ def load() -> C.CDLL:
     L.tdoa_set_bin_weights.argtypes = [P, P]
     L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]
     L.tdoa_get_bin_weights.argtypes = [P, P]
+    L.tdoa_set_sample_format.argtypes = [P, C.c_int]
+    L.tdoa_get_sample_format.argtypes = [P, C.POINTER(C.c_int)]
     # reference-named per-frame symbols
     L.microphones_init.argtypes = []
     L.rolling_buffer_init.argtypes = [C.POINTER(RollingBuffer)]

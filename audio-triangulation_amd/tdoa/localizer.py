@@ -40,6 +40,9 @@ class Localizer:
 
     engine: "direct" (exact int64, the reference's semantics bit-for-bit) or
     "gcc_phat" (fp32 FFT cross-spectrum with PHAT weighting).
+    sample_format: "adc8" (the reference's 8-bit ADC front end: the low byte of
+    every sample) or "pcm16" (full-range int16 frames, GCC_PHAT only; see
+    set_sample_format).
     """
 
     def __init__(self, num_mics: int = 3, frame_len: int = 1024,
@@ -48,7 +51,7 @@ class Localizer:
                  grid_half_h: int = 50, grid_scale: float = 24.0,
                  height_offset: float = 1.2, speed_of_sound: float = 343.0,
                  window_q15=None, phat_eps: float = 1e-12, device: int = 0,
-                 band_hz=None, band_taper_hz: float = 0.0):
+                 band_hz=None, band_taper_hz: float = 0.0, sample_format: str = "adc8"):
         L = load()
         cfg = Config()
         L.tdoa_config_default(C.byref(cfg))
@@ -85,12 +88,14 @@ class Localizer:
         self.dims = Geometry(*[x.value for x in d])
         self.grid_W = 2 * grid_half_w + 1
         self.grid_half_w, self.grid_half_h, self.grid_scale = grid_half_w, grid_half_h, grid_scale
-        if band_hz is not None:
-            try:
+        try:
+            if band_hz is not None:
                 self.set_band(band_hz[0], band_hz[1], band_taper_hz)
-            except Exception:
-                self.close()
-                raise
+            if sample_format != "adc8":
+                self.set_sample_format(sample_format)
+        except Exception:
+            self.close()
+            raise
 
     # ---------------------------------------------------------- lifetime
     def close(self):
@@ -157,6 +162,24 @@ class Localizer:
         w = np.zeros(self.dims.N + 1, np.float32)
         check(load().tdoa_get_bin_weights(self._ctx, w.ctypes.data_as(C.c_void_p)), "tdoa_get_bin_weights")
         return w
+
+    # ---------------------------------------------------------- 16-bit input
+    def set_sample_format(self, fmt: str) -> None:
+        """"adc8": the 8-bit ADC front end ((x - off) << 8 in int16, the low
+        byte of every sample), every kernel and bit as before.  "pcm16":
+        full-range int16 frames, s = ((x - floor mean) * W) >> 15 without the
+        wrap (tdoa_set_sample_format; GCC_PHAT only).  Synchronous; not while
+        a call of this context is in flight."""
+        if fmt not in _lib.SAMPLE_FORMATS:
+            raise ValueError(f"sample_format must be one of {sorted(_lib.SAMPLE_FORMATS)}, got {fmt!r}")
+        check(load().tdoa_set_sample_format(self._ctx, _lib.SAMPLE_FORMATS[fmt]), "tdoa_set_sample_format")
+
+    @property
+    def sample_format(self) -> str:
+        """The format in force: "adc8" or "pcm16"."""
+        v = C.c_int()
+        check(load().tdoa_get_sample_format(self._ctx, C.byref(v)), "tdoa_get_sample_format")
+        return {n: k for k, n in _lib.SAMPLE_FORMATS.items()}[v.value]
 
     # ---------------------------------------------------------- compute
     def alloc_outputs(self, B: int, scores: bool = False, grid: bool = True,

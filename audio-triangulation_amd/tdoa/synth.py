@@ -130,6 +130,33 @@ def interferer_frames(B: int, M: int, N: int, fs: int, S: int, seed: int, target
     return frames.contiguous(), pair[0], pair[1]
 
 
+def pcm16_frames(B: int, M: int, N: int, S: int, seed: int, delays, src_std: float = 3000.0,
+                 noise_std: float = 600.0, dc=None, device: str | torch.device = "cpu"):
+    """Full-range 16-bit frames of one white source (the 16-bit PCM scenario).
+    Per frame a Gaussian source of N + 4S samples and standard deviation
+    `src_std` counts; mic m reads it delayed by the integer delays[m]
+    (|delay| <= 2S), plus N(0, noise_std) white noise, plus the offset dc[m]
+    (default 0), rounded and clipped to int16.
+    Draw order (numpy default_rng(seed)): source [B][N + 4S], noise [B][M][N].
+    Returns (frames int16 [B][M][N] on `device`, pair lags int32 [P]); pair
+    (i, j) in lexicographic order has lag delays[j] - delays[i], the sign of the
+    engines' best lags."""
+    rng = np.random.default_rng(int(seed))
+    T, pad = N + 4 * S, 2 * S
+    src = rng.standard_normal((B, T)) * float(src_std)
+    x = rng.standard_normal((B, M, N)) * float(noise_std)
+    lag = np.asarray(delays, np.int64)[:M]
+    assert lag.size == M and np.abs(lag).max() <= pad, "one delay per mic, |delay| <= 2S"
+    off = np.zeros(M) if dc is None else np.asarray(dc, np.float64)[:M]
+    assert off.size == M, "one offset per mic"
+    n = np.arange(N)
+    for m in range(M):
+        x[:, m] += src[:, pad + n - lag[m]] + off[m]
+    frames = torch.from_numpy(np.clip(np.rint(x), -32768, 32767).astype(np.int16)).to(torch.device(device))
+    pair = np.array([lag[j] - lag[i] for i in range(M) for j in range(i + 1, M)], np.int32)
+    return frames.contiguous(), pair
+
+
 def full_range_frames(B: int, M: int, N: int, seed: int, device="cpu") -> torch.Tensor:
     dev = torch.device(device)
     g = torch.Generator(device=dev)

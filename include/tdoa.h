@@ -82,7 +82,10 @@ typedef struct tdoa_config {
     const int32_t *window_q15;
     /* GCC_PHAT: per-mic soft floor, U_m = X_m / sqrt(|X_m|^2 + phat_eps),
      * R_ij = conj(U_i) U_j, with samples scaled by 2^-15 and X the 2N-point
-     * spectrum; default 1e-12. */
+     * spectrum; default 1e-12.  The scale is 2^-15 in both sample formats
+     * (tdoa_set_sample_format) and TDOA_SAMPLES_PCM16 has no << 8: a frame of
+     * 8-bit-sized samples is 256 times smaller there than in TDOA_SAMPLES_ADC8,
+     * so the same phat_eps floors it 2^16 times harder in |X|^2. */
     float phat_eps;
 } tdoa_config;
 
@@ -260,6 +263,40 @@ int tdoa_set_bin_weights(tdoa_ctx *ctx, const float *w);
 int tdoa_set_band_hz(tdoa_ctx *ctx, double lo_hz, double hi_hz, double taper_hz);
 /* Host copy of the table in force; all 1.0f when none is set. */
 int tdoa_get_bin_weights(const tdoa_ctx *ctx, float *w /* [N+1] */);
+
+/* ---- 16-bit PCM input (GCC_PHAT) ----
+ * The default front end is the firmware's 8-bit ADC path: (x - off) << 8 in
+ * int16 keeps the low byte of every sample.  TDOA_SAMPLES_PCM16 takes
+ * full-range int16 frames instead.  Per mic row x[0..N):
+ *   off  = floor(sum(x) / N)             arithmetic shift; off in [-32768, 32767]
+ *   y[n] = x[n] - off                    int32, no wrap; |y| <= 65535
+ *   s[n] = (y[n] * W[n]) >> 15           int32 arithmetic shift (floor), W the Q15 window
+ * and s enters the FFT where the 8-bit prepared sample does, in the same
+ * units (x = s / 2^15): phat_eps, the lag rule, prior, gate, grid, least
+ * squares, peaks and the heat map are defined on the scores and do not change.
+ * Kernels: 3 x 1024 runs the fused k_p1k_pcm16 (it solves the grid: one HIP
+ * stream per context is not required, two streams may overlap as with
+ * k_p1k_lean); 4 x 2048, 8 x 2048, 3 x 4096 and 4 x 4096 run k_f16_pcm16;
+ * every other shape, and every shape with a bin-weight table, runs the
+ * two-pass route (k_phat_spectra_pcm16, k_phat_pairs).  A/B switches that pick
+ * other kernels (TDOA_P1K, TDOA_F16, TDOA_F16_FG) are ignored in this format. */
+typedef enum tdoa_sample_format {
+    TDOA_SAMPLES_ADC8 = 0,  /* default: the reference's 8-bit path, every kernel and bit as without this section */
+    TDOA_SAMPLES_PCM16 = 1  /* full-range int16, the definition above; GCC_PHAT only */
+} tdoa_sample_format;
+/* Synchronous; must not be called while a call on the context is in flight.
+ * TDOA_ERR_INVALID for a NULL ctx, an unknown value, or PCM16 on a DIRECT
+ * context: the format in force stays.  ADC8 is accepted on any context and
+ * returns it to the kernels and bits it produced before.  A shape whose 8-bit
+ * kernel is fused but whose PCM16 route has two passes gets the spectrum
+ * scratch (128 MiB, freed by tdoa_destroy) on first need, as
+ * tdoa_set_bin_weights does.  tdoa_correlate_prepared and the per-frame
+ * reference symbols run the integer path whatever the format;
+ * tdoa_stream_create on a PCM16 context is TDOA_ERR_INVALID (the capture ring
+ * is 8-bit by definition), and a pipeline created before the switch keeps its
+ * 8-bit parameters. */
+int tdoa_set_sample_format(tdoa_ctx *ctx, int format);
+int tdoa_get_sample_format(const tdoa_ctx *ctx, int *format);
 
 /* Host helper: decay of correlations.c:42-43 from integer-us timestamps. */
 float tdoa_decay_us(uint64_t now_us, uint64_t last_us);

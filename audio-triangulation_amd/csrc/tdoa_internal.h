@@ -93,7 +93,8 @@ struct tdoa_peaks_kout {
 struct tdoa_stream_params {
     int32_t M, N, H, log2N, fs;
     int64_t capture_len;      // samples per stream in the capture ring
-    const uint8_t *capture;   // [S][capture_len][M] 8-bit ADC bytes, round-robin
+    const uint8_t *capture;   // [S][capture_len][M] 8-bit ADC bytes, round-robin; of a PCM16
+                              // pipeline int16 samples (k_stream_trigger16, k_stream_phat_pcm16 cast it)
     int64_t *pos;             // [1] samples consumed (device clock)
     int64_t *ring_start;      // [S] sample index of the last trigger (rings restart there)
     int32_t *count;           // [1] frames triggered this step
@@ -180,19 +181,23 @@ size_t tdoa_stream_trigger_lds(int M, int N, int H);
 // *by_id: the launch wrote each triggered frame at its stream's index
 // (k_stream_trigger_p) instead of its compact slot -- the layout DIRECT reads
 int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *stream, bool *by_id);
+// the trigger on an int16 ring (k_stream_trigger16; sp.capture holds int16):
+// thr = trigger_var * (N/2)^2; firing streams are listed only (by_id form)
+int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_t thr, void *stream);
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,
                               const tdoa_stream_kout &out, int64_t S, void *stream);
 // the GCC_PHAT hop after the trigger (tdoa_stream_phat.hip, k_stream_phat):
 // its dynamic LDS, whether the shape fits, the launch size for S streams
 // (resident workgroups, capped by `cap` > 0), and the launch -- est is the
 // float EMA state [S][P][K] (sp.est, sp.fresh* are not read), by_id as
-// tdoa_launch_stream_trigger answered
+// tdoa_launch_stream_trigger answered; pcm16: the int16-ring kernel
+// (k_stream_phat_pcm16, after tdoa_launch_stream_trigger16; by_id is not read)
 size_t tdoa_stream_phat_lds(const tdoa_kparams &kp);
 bool tdoa_stream_phat_fits(const tdoa_kparams &kp);
-int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap);
+int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16 = false);
 int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
                             float *est, float *max_Lf, int64_t S, bool by_id, float phat_eps, int grid,
-                            void *stream);
+                            void *stream, bool pcm16 = false);
 int tdoa_launch_average(const tdoa_kparams &kp, int64_t S, int64_t *est,
                         const int64_t *fresh, const float *decay, int32_t *best,
                         const tdoa_kout *solve, void *stream);

@@ -7,7 +7,9 @@
 //   other slot for the next hop (a memset node cost 3.9 us per hop), so the
 //   two parities are two captured graphs.
 // A GCC_PHAT pipeline runs the same trigger, then k_stream_phat
-// (tdoa_stream_phat.hip): float scores, float EMA state, max_Lf.
+// (tdoa_stream_phat.hip): float scores, float EMA state, max_Lf.  On an int16
+// ring (tdoa_stream_create_pcm16) it runs k_stream_trigger16, then
+// k_stream_phat_pcm16.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -61,6 +63,9 @@ struct tdoa_stream {
     float *est_f = nullptr; // ... its EMA state [S][P][K] (sp.est is null)
     float phat_eps = 0.0f;
     int phat_grid = 1;      // k_stream_phat's launch size
+    bool pcm16 = false;     // int16 capture ring (tdoa_stream_create_pcm16): k_stream_trigger16,
+                            // k_stream_phat_pcm16; the format is the pipeline's from creation on
+    int64_t trig_thr = 0;   // ... its trigger threshold, trigger_var * (N/2)^2
 };
 
 namespace {
@@ -88,7 +93,8 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
     sp.count = st->sp.count + par;
     sp.count_next = st->sp.count + (1 - par);
     bool by_id = false;  // where DIRECT finds the frames: the capture ring or compact copies
-    int rc = tdoa_launch_stream_trigger(sp, st->S, s, &by_id);
+    int rc = st->pcm16 ? tdoa_launch_stream_trigger16(sp, st->S, st->trig_thr, s)
+                       : tdoa_launch_stream_trigger(sp, st->S, s, &by_id);
     if (rc)
         return rc;
     if (st->phat) {
@@ -99,7 +105,7 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
         kp.bin_lo = ck->bin_lo;
         kp.bin_hi = ck->bin_hi;
         return tdoa_launch_stream_phat(sp, kp, to_kout(out), st->est_f, out.max_Lf, st->S, by_id, st->phat_eps,
-                                       st->phat_grid, s);
+                                       st->phat_grid, s, st->pcm16);
     }
     tdoa_kparams kp = st->kp;
     if (by_id) {  // listed only: DIRECT stages each frame from its stream's ring
@@ -134,38 +140,48 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
     return tdoa_launch_stream_update(sp, st->kp, to_kout(out), st->S, s);
 }
 
-}  // namespace
-
-extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
-                                  const uint8_t *capture, int64_t capture_len, int use_graph,
-                                  tdoa_stream **out)
+// tdoa_stream_create (pcm16 false: `capture` holds bytes) and
+// tdoa_stream_create_pcm16 (int16 samples, GCC_PHAT in PCM16 format only)
+int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t hop, const void *capture,
+                  int64_t capture_len, bool pcm16, int64_t trigger_var, int use_graph, tdoa_stream **out)
 {
     if (!ctx || !out || !capture)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: NULL argument");
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
     const int engine = tdoa_ctx_engine(ctx);
     if (engine != TDOA_ENGINE_DIRECT && engine != TDOA_ENGINE_GCC_PHAT)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: needs a DIRECT or GCC_PHAT context");
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: needs a DIRECT or GCC_PHAT context", fn);
     const bool phat = engine == TDOA_ENGINE_GCC_PHAT;
     const tdoa_kparams &kp = *tdoa_ctx_kparams(ctx);
     const int M = kp.M, N = kp.N, P = kp.P, K = kp.K;
-    if (kp.pcm16)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: the capture ring is 8-bit; the context's sample "
-                                           "format is PCM16 (tdoa_set_sample_format)");
+    if (pcm16) {
+        if (!phat)
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: an int16 capture ring needs a GCC_PHAT context (DIRECT stays 8-bit)",
+                             fn);
+        if (!kp.pcm16)
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: the context's sample format is ADC8; set TDOA_SAMPLES_PCM16 first "
+                                               "(tdoa_set_sample_format)", fn);
+        if (trigger_var < 0 || trigger_var > ((int64_t)1 << 30))
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: trigger_var %lld outside [0, 2^30]", fn, (long long)trigger_var);
+        if (((uintptr_t)capture & 1) != 0)
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: capture is not 2-byte aligned", fn);
+    } else if (kp.pcm16) {
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: this capture ring is 8-bit and the context's sample format is PCM16 "
+                                           "(tdoa_set_sample_format): tdoa_stream_create_pcm16 takes int16 rings", fn);
+    }
     if (phat && !tdoa_stream_phat_fits(kp))
         return tdoa_fail(TDOA_ERR_INVALID,
-                         "tdoa_stream_create: GCC_PHAT with %d mics x frame_len %d needs %zu bytes of LDS per "
+                         "%s: GCC_PHAT with %d mics x frame_len %d needs %zu bytes of LDS per "
                          "workgroup (limit 160 KiB)",
-                         M, N, tdoa_stream_phat_lds(kp));
+                         fn, M, N, tdoa_stream_phat_lds(kp));
     if (num_streams < 1)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: num_streams %d < 1", num_streams);
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: num_streams %d < 1", fn, num_streams);
     if (hop < 1 || hop > N || hop > 4096)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: hop %d outside [1, frame_len]", hop);
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: hop %d outside [1, frame_len]", fn, hop);
     if (capture_len < (int64_t)N + 2 * hop)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: capture_len %lld < frame_len + 2 hop",
-                     (long long)capture_len);
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: capture_len %lld < frame_len + 2 hop", fn, (long long)capture_len);
     if (tdoa_stream_trigger_lds(M, N, hop) > 150 * 1024)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_create: (frame_len + hop) x mics too large");
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: (frame_len + hop) x mics too large", fn);
     const int dev = tdoa_ctx_device(ctx);
     HIP_TRY(hipSetDevice(dev));
 
@@ -176,11 +192,13 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->kp = kp;
     st->use_graph = use_graph;
     st->phat = phat;
+    st->pcm16 = pcm16;
+    st->trig_thr = pcm16 ? trigger_var * (int64_t)(N / 2) * (N / 2) : 0;  // <= 2^30 * 2^22
     if (phat) {
         st->phat_eps = tdoa_ctx_phat_eps(ctx);
         // TDOA_STREAM_PHAT_GRID=n caps k_stream_phat's launch size (A/B runs)
         const char *cap = std::getenv("TDOA_STREAM_PHAT_GRID");
-        st->phat_grid = tdoa_stream_phat_grid(kp, num_streams, cap ? std::atoi(cap) : 0);
+        st->phat_grid = tdoa_stream_phat_grid(kp, num_streams, cap ? std::atoi(cap) : 0, pcm16);
     }
     const size_t S = (size_t)num_streams;
     // carve: 256-B aligned sub-buffers of one allocation
@@ -192,12 +210,12 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     };
     // (a GCC_PHAT pipeline keeps the frame's scores on chip: no fresh* buffers, float EMA state)
     const size_t o_pos = take(8), o_count = take(8), o_rs = take(S * 8), o_ids = take(S * 4),
-                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(S * M * N),
+                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(pcm16 ? 0 : S * M * N),
                  o_fresh = take(phat ? 0 : S * P * K * 8), o_fl = take(phat ? 0 : S * P * 4),
                  o_fg = take(phat ? 0 : S), o_est = take(S * P * K * (phat ? 4 : 8)), o_last = take(S * 8),
                  o_stats = take(16);
     if (st->mem.alloc(off) != hipSuccess)
-        return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_create: %zu bytes of stream state", off);
+        return tdoa_fail(TDOA_ERR_NOMEM, "%s: %zu bytes of stream state", fn, off);
     char *b = st->mem.get<char>();
     tdoa_stream_params &sp = st->sp;
     sp.M = M;
@@ -206,14 +224,14 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.log2N = kp.log2N;
     sp.fs = tdoa_ctx_rate(ctx);
     sp.capture_len = capture_len;
-    sp.capture = capture;
+    sp.capture = static_cast<const uint8_t *>(capture);
     sp.pos = (int64_t *)(b + o_pos);
     sp.count = (int32_t *)(b + o_count);
     sp.ring_start = (int64_t *)(b + o_rs);
     sp.ids = (int32_t *)(b + o_ids);
     sp.end = (int64_t *)(b + o_end);
     sp.ring_at = (int64_t *)(b + o_at);
-    sp.frames = (int16_t *)(b + o_frames);
+    sp.frames = pcm16 ? nullptr : (int16_t *)(b + o_frames);
     sp.fresh = phat ? nullptr : (int64_t *)(b + o_fresh);
     sp.fresh_lags = phat ? nullptr : (int32_t *)(b + o_fl);
     sp.fresh_gate = phat ? nullptr : (uint8_t *)(b + o_fg);
@@ -222,9 +240,26 @@ extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.last = (uint64_t *)(b + o_last);
     sp.stats = (int64_t *)(b + o_stats);
     if (hipMemset(st->mem.get<void>(), 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-        return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_create: clearing state failed");
+        return tdoa_fail(TDOA_ERR_HIP, "%s: clearing state failed", fn);
     *out = st.release();
     return TDOA_OK;
+}
+
+}  // namespace
+
+extern "C" int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
+                                  const uint8_t *capture, int64_t capture_len, int use_graph,
+                                  tdoa_stream **out)
+{
+    return stream_create("tdoa_stream_create", ctx, num_streams, hop, capture, capture_len, false, 0, use_graph, out);
+}
+
+extern "C" int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
+                                        const int16_t *capture, int64_t capture_len, int64_t trigger_var,
+                                        int use_graph, tdoa_stream **out)
+{
+    return stream_create("tdoa_stream_create_pcm16", ctx, num_streams, hop, capture, capture_len, true, trigger_var,
+                         use_graph, out);
 }
 
 namespace {

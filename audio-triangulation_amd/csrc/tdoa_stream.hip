@@ -38,6 +38,7 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int MAX_CAND = 16;  // hop <= 4096 candidates, TPB per pass
+constexpr int TRIG16_LB = 16; // k_stream_trigger16: ring loads in flight per thread
 
 // inclusive block scan of per-thread totals (int32 and int64 together)
 __device__ __forceinline__ void block_exclusive_scan(int &v1, long long &v2, int *s1,
@@ -195,6 +196,155 @@ __global__ void __launch_bounds__(TPB) k_stream_trigger(tdoa_stream_params sp)
         dst[i] = (uint32_t)(uint8_t)x[0] | (uint32_t)(uint8_t)x[1] << 8 | (uint32_t)(uint8_t)x[2] << 16 |
                  (uint32_t)(uint8_t)x[3] << 24;
     }
+}
+
+// ------------------------------------------------- the trigger on int16 rings
+// tdoa_stream_create_pcm16 (include/tdoa.h): k_stream_trigger's rule on int16
+// samples with the caller's threshold, thr = trigger_var * (N/2)^2.  sp.capture
+// points at int16 [S][capture_len][M] (2-byte loads: a stream's ring starts at
+// s * capture_len * M * 2 bytes, 4-byte aligned only when capture_len * M is
+// even).  One workgroup per stream, the same LDS prefix sums; per candidate one
+// int64 accumulator, sum_m pw(m, O) - pw(m, I): |pw| <= h^2 2^30 = 2^52 at
+// h = 2048, 2^55 over 8 mics, the prefix sums of x below (N + H) 2^15 <= 2^28
+// and those of x^2 below 2^43.  A firing stream is listed (ids, end, ring_at):
+// k_stream_phat<PCM16> stages the frame from the ring, no copy is written.
+__global__ void __launch_bounds__(TPB) k_stream_trigger16(tdoa_stream_params sp, long long thr)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0 && sp.count_next)
+        *sp.count_next = 0;  // the next hop's counter (last read by the previous hop)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int M = sp.M, N = sp.N, H = sp.H, L = N + H - 1, tid = threadIdx.x;
+    int16_t *xs = (int16_t *)smem;                                   // [M][L]
+    size_t o = (((size_t)M * L * 2) + 15) & ~(size_t)15;
+    int *Q1 = (int *)(smem + o);                                      // [L + 1]
+    o += (((size_t)(L + 1) * 4) + 15) & ~(size_t)15;
+    long long *Q2 = (long long *)(smem + o);                          // [L + 1]
+    __shared__ int sc1[TPB / 64];
+    __shared__ long long sc2[TPB / 64];
+    __shared__ int first;
+
+    const int64_t s = blockIdx.x;
+    const int64_t pos = *sp.pos;           // samples consumed before this hop
+    const int64_t rs = sp.ring_start[s];
+    // full ring: at least N samples since the last trigger
+    const int64_t amin = rs + N - pos - 1;
+    if (amin >= H)
+        return;  // fired during the previous hop: no candidate of this one is eligible
+    const int64_t base = pos + 1 - N;      // stream index of local sample 0
+    const int64_t cl = sp.capture_len;
+    const int16_t *cap = reinterpret_cast<const int16_t *>(sp.capture) + (size_t)s * cl * M;
+    int64_t j0 = base % cl;
+    if (j0 < 0)
+        j0 += cl;
+    // local samples l = 0..L-1 <-> stream index base + l (zero before the stream
+    // starts): ring elements e0 + i (i = l M + m), contiguous modulo the ring's
+    // cl M, de-interleaved into xs.  TRIG16_LB loads are in flight per thread
+    // before the first is used (one load per trip waited out its latency 18
+    // times at config 5), and a thread's (l, m) advance by TPB elements per
+    // load without a division.
+    {
+        const int tot = L * M;  // <= 8191 * 8
+        const int64_t ring = cl * M, e0 = j0 * M;  // e0 + tot < 2 ring: L < cl
+        const int iw = ring - e0 < tot ? (int)(ring - e0) : tot;  // elements before the ring's end
+        const int nz = base < 0 ? (base < -(int64_t)L ? L : (int)-base) : 0;  // samples before the stream's start
+        const int dl = TPB / M, dm = TPB - dl * M;
+        int l = tid / M, m = tid - l * M;
+        for (int i0 = tid; i0 < tot; i0 += TRIG16_LB * TPB) {
+            int16_t v[TRIG16_LB];
+#pragma unroll
+            for (int k = 0; k < TRIG16_LB; k++) {
+                const int i = i0 + k * TPB;
+                const int64_t e = (i < iw ? e0 : e0 - ring) + i;  // in [0, ring)
+                v[k] = i < tot ? cap[e] : (int16_t)0;
+            }
+#pragma unroll
+            for (int k = 0; k < TRIG16_LB; k++) {
+                if (i0 + k * TPB < tot)
+                    xs[m * L + l] = l < nz ? (int16_t)0 : v[k];
+                l += dl;
+                m += dm;
+                if (m >= M) {
+                    m -= M;
+                    l++;
+                }
+            }
+        }
+    }
+    if (tid == 0)
+        first = INT_MAX;
+    __syncthreads();
+
+    // per candidate a (frame = local [a, a + N), end = pos + 1 + a): sum over
+    // mics of the older half's power minus the newer half's
+    const int hb = sp.log2N - 1, h = N >> 1;
+    long long dp[MAX_CAND];
+#pragma unroll
+    for (int c = 0; c < MAX_CAND; c++)
+        dp[c] = 0;
+    const int per = (L + 1 + TPB - 1) / TPB;  // prefix entries per thread
+    for (int m = 0; m < M; m++) {
+        const int16_t *x = xs + m * L;
+        int t1 = 0;
+        long long t2 = 0;
+        const int l0 = tid * per;
+        for (int k = 0; k < per; k++) {
+            const int l = l0 + k;
+            if (l < L) {
+                const int v = x[l];
+                t1 += v;
+                t2 += (long long)(v * v);  // |v| <= 2^15: v^2 fits int32
+            }
+        }
+        int e1 = t1;
+        long long e2 = t2;
+        block_exclusive_scan(e1, e2, sc1, sc2);
+        // entries l0 .. l0 + per - 1 of the L + 1 (per TPB >= L + 1: entry L, the total, is some thread's)
+        for (int k = 0; k < per; k++) {
+            const int l = l0 + k;
+            if (l <= L) {
+                Q1[l] = e1;
+                Q2[l] = e2;
+            }
+            if (l < L) {
+                const int v = x[l];
+                e1 += v;
+                e2 += (long long)(v * v);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < MAX_CAND; c++) {
+            const int a = tid + TPB * c;
+            if (a < H) {
+                const long long q1a = Q1[a], q1h = Q1[a + h], q1n = Q1[a + N];
+                const long long so1 = q1h - q1a, si1 = q1n - q1h;
+                const long long d2 = (Q2[a + h] - Q2[a]) - (Q2[a + N] - Q2[a + h]);
+                // h (so2 - si2) - so1^2 + si1^2
+                dp[c] += (long long)((unsigned long long)d2 << hb) + (si1 - so1) * (si1 + so1);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int c = 0; c < MAX_CAND; c++) {
+        const int a = tid + TPB * c;
+        if (a < H && a >= amin && dp[c] > thr) {
+            atomicMin(&first, a);
+            break;  // candidates grow with c: this thread's first is its best
+        }
+    }
+    __syncthreads();
+    const int a = first;
+    if (a == INT_MAX || tid != 0)
+        return;
+    const int slot = atomicAdd(sp.count, 1);
+    const int64_t end = pos + 1 + a;
+    if (slot < (int)gridDim.x) {  // one slot per stream (see k_stream_trigger_p)
+        sp.ids[slot] = (int32_t)s;
+        sp.end[slot] = end;
+        sp.ring_at[slot] = j0 + a >= cl ? j0 + a - cl : j0 + a;
+    }
+    sp.ring_start[s] = end;
 }
 
 // ------------------------------------------- register trigger scan (N = 2H)
@@ -760,6 +910,18 @@ int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *st
     hipLaunchKernelGGL(k_stream_trigger, dim3((unsigned)S), dim3(TPB), lds, st, sp);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger launch");
+}
+
+int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_t thr, void *stream)
+{
+    if (sp.H > TPB * MAX_CAND)
+        return tdoa_set_error(-1, "stream: hop too large");
+    const size_t lds = tdoa_stream_trigger_lds(sp.M, sp.N, sp.H);  // xs is int16 in both triggers
+    if (lds > 150 * 1024)
+        return tdoa_set_error(-1, "stream: (frame_len + hop) x mics exceeds the LDS budget");
+    hipLaunchKernelGGL(k_stream_trigger16, dim3((unsigned)S), dim3(TPB), lds, (hipStream_t)stream, sp, (long long)thr);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger16 launch");
 }
 
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,

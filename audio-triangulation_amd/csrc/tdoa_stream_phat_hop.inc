@@ -1,0 +1,262 @@
+// tdoa_stream_phat_hop.inc -- the body of k_stream_phat (8-bit capture rings) and
+// k_stream_phat_pcm16 (int16 rings, tdoa_stream_create_pcm16), as text: it
+// reads the kernel's parameters (sp, kp, out, est_all, max_Lf, nstreams, e2),
+// by_id and the constant PCM16 of the including scope.  PCM16: sp.capture
+// points at int16 samples, the slot's frame is staged from the ring
+// (k_stream_trigger16 lists firing streams only; by_id is not read) and the
+// front end is phat_front_end<true>; everything after it is the same text.
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int N = kp.N, M = kp.M, P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, nwaves = TPB / 64;
+    f2 *U = (f2 *)smem;                // [M][N] unit spectra (slot 0 = bins 0 and N); a mic's raw samples before
+    f2 *buf = U + (size_t)M * N;       // [N] FFT work buffer
+    float *Wf = (float *)(buf + N);    // [P][K] the frame's weighted scores
+    float *E = Wf + P * K;             // [P][K] the stream's EMA scores
+    __shared__ int red[TPB / 64];
+    __shared__ float redv[TPB / 64];
+    __shared__ int redi[TPB / 64];
+    __shared__ float sc[128];
+    __shared__ int lag_s[TDOA_MAX_PAIRS];
+
+    // at most one slot per stream: a corrupted counter cannot index past [S]
+    const int cnt_raw = *sp.count;
+    const int cnt = cnt_raw < 0 ? 0 : (cnt_raw > nstreams ? nstreams : cnt_raw);
+    if (blockIdx.x == 0 && tid == 0) {
+        *sp.pos += sp.H;  // the trigger kernel has read it
+        sp.stats[0] += cnt;
+        if (out.count)
+            *out.count = cnt;
+    }
+    const uint32_t *win = reinterpret_cast<const uint32_t *>(kp.window);
+    const int64_t ring_bytes = sp.capture_len * M;
+    int ngated = 0;  // this workgroup's gated frames
+    SP_T0();
+    // persistent over the compact batch (its size is only known on the device)
+    for (int slot = blockIdx.x; slot < cnt; slot += gridDim.x) {
+        __syncthreads();  // the previous slot's tables and reductions are consumed
+        SP_MARK(3);
+        const int s = sp.ids[slot];
+        const int64_t end = sp.end[slot];
+
+        // ---- the frame's samples as int16, mic m's row at the start of U[m]
+        if constexpr (PCM16) {
+            // ring samples [at, at + N) of the stream, [n][M] -> [m][n], wrapping
+            // at the ring's end.  A thread takes samples 2q, 2q + 1 of one mic
+            // (m fastest: a wave's 2-byte loads cover contiguous ring bytes; a
+            // ring need not start 4-byte aligned) and writes them as one LDS word
+            const int64_t cl = sp.capture_len;
+            const int16_t *cap = reinterpret_cast<const int16_t *>(sp.capture) + (size_t)s * cl * M;
+            const int64_t at = sp.ring_at[slot];
+            for (int i = tid; i < (N >> 1) * M; i += TPB) {
+                const int q = i / M, m = i - q * M;
+                int64_t j0 = at + 2 * q;  // at < cl, 2q < N <= cl: one wrap at most
+                if (j0 >= cl)
+                    j0 -= cl;
+                const int64_t j1 = j0 + 1 >= cl ? 0 : j0 + 1;
+                const uint32_t lo = (uint16_t)cap[(size_t)j0 * M + m], hi = (uint16_t)cap[(size_t)j1 * M + m];
+                reinterpret_cast<uint32_t *>(U + (size_t)m * N)[q] = lo | hi << 16;
+            }
+        } else if (by_id) {
+            // ring bytes [at * M, at * M + N * M) of the stream, wrapping at the
+            // ring's end; byte loads: a ring need not start 4-byte aligned
+            const uint8_t *cap = sp.capture + (size_t)s * ring_bytes;
+            const int64_t b0 = sp.ring_at[slot] * M;
+            for (int i = tid; i < N * M; i += TPB) {
+                const int l = i / M, m = i - l * M;
+                int64_t b = b0 + i;
+                if (b >= ring_bytes)
+                    b -= ring_bytes;
+                reinterpret_cast<int16_t *>(U + (size_t)m * N)[l] = (int16_t)cap[b];
+            }
+        } else {
+            const uint32_t *src =
+                reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(sp.frames) + (size_t)slot * M * N);
+            for (int i = tid; i < M * N / 4; i += TPB) {
+                const int m = (4 * i) / N, n = 4 * i - m * N;
+                const uint32_t w = src[i];
+                uint32_t *dst = reinterpret_cast<uint32_t *>(U + (size_t)m * N) + (n >> 1);
+                dst[0] = (w & 0xFFu) | ((w >> 8) & 0xFFu) << 16;
+                dst[1] = ((w >> 16) & 0xFFu) | (w >> 24) << 16;
+            }
+        }
+        __syncthreads();
+        SP_MARK(0);
+
+        // ---- per mic: front end, FFT_N, split, unit spectrum
+        for (int m = 0; m < M; m++) {
+            f2 *row = U + (size_t)m * N;
+            phat_front_end<PCM16>(reinterpret_cast<const uint32_t *>(row), win, N, kp.log2N, red, buf);
+            fft_inplace<false>(buf, N, kp.tw);
+            phat_split<true>(buf, row, N, kp.tw2, e2);  // U = X / sqrt(|X|^2 + e2)
+            __syncthreads();  // buf and red are free for the next mic
+        }
+
+        SP_MARK(1);
+        // ---- per pair: cross spectrum, inverse FFT_N, lags -S..S, first maximum, prior
+        const float *bw = kp.bin_w;
+        for (int p = 0; p < P; p++) {
+            const f2 *Ui = U + (size_t)kp.pair_i[p] * N;
+            const f2 *Uj = U + (size_t)kp.pair_j[p] * N;
+            for (int k = tid; k <= N / 2; k += TPB) {  // R = conj(U_i) U_j
+                const int kn = (N - k) & (N - 1);
+                f2 ik = Ui[k], in = Ui[kn], jk = Uj[k], jn = Uj[kn];
+                if (k == 0) {  // slot 0 = (U[0], U[N]), both real
+                    ik = f2{ik.x, 0.0f};
+                    jk = f2{jk.x, 0.0f};
+                    in = f2{in.y, 0.0f};
+                    jn = f2{jn.y, 0.0f};
+                }
+                f2 Rk = cmul(conj2(ik), jk), Rn = cmul(conj2(in), jn);
+                if (bw) {  // band-limited: bin k by w[k], bin N - k by w[N - k]
+                    Rk = bw[k] * Rk;
+                    Rn = bw[N - k] * Rn;
+                }
+                phat_fold(buf, N, k, Rk, Rn, kp.tw2);
+            }
+            __syncthreads();
+            fft_inplace<true>(buf, N, kp.tw);
+            phat_lags(buf, sc, N, K, S);
+            if (tid < 64) {
+                const int k1 = lane, k2 = lane + 64;
+                const float v1 = k1 < K ? sc[k1] : -INFINITY, v2 = k2 < K ? sc[k2] : -INFINITY;
+                const int bk = wave_first_max(v1, v2, lane, K);
+                prior_weighted(Wf + p * K, kp.prior, v1, v2, lane, K, bk);
+                if (lane == 0)
+                    lag_s[p] = bk - S;
+            }
+            __syncthreads();  // sc and buf are free for the next pair
+        }
+
+        SP_MARK(2);
+#ifdef TDOA_DIAG
+        sp_acc_[4] += 1;
+#endif
+        // ---- gate and the slot's record
+        int g2 = 0;
+        for (int p = 0; p < P; p++)
+            g2 += lag_s[p] * lag_s[p];
+        const bool gated = g2 > 4;  // sample_compute.h:124-134
+        if (out.lags) {
+            for (int p = tid; p < P; p += TPB)
+                out.lags[(size_t)slot * P + p] = lag_s[p];
+        }
+        if (tid == 0) {
+            if (out.stream_id)
+                out.stream_id[slot] = s;
+            if (out.end)
+                out.end[slot] = end;
+            if (out.gate)
+                out.gate[slot] = gated ? 1 : 0;
+        }
+        if (!gated) {  // sample_compute.h:134: only gated frames update
+            if (tid == 0 && out.cell)
+                out.cell[slot] = -1;
+            continue;
+        }
+        ngated++;
+
+        // ---- float EMA on the stream's scores, the rows' first maxima
+        const uint64_t now = (uint64_t)end * 1000000u / (uint64_t)sp.fs;
+        const float dec = tdoa_decay_dev(now, sp.last[s]);
+        float *est = est_all + (size_t)s * P * K;
+        for (int i = tid; i < P * K; i += TPB) {
+            const float nv = ema_step(est[i], Wf[i], dec);
+            est[i] = nv;
+            E[i] = nv;
+        }
+        __syncthreads();
+        if (tid == 0)
+            sp.last[s] = now;
+        if (out.ema_best) {
+            for (int p = wave; p < P; p += nwaves) {
+                const int k1 = lane, k2 = lane + 64;
+                const float v1 = k1 < K ? E[p * K + k1] : -INFINITY, v2 = k2 < K ? E[p * K + k2] : -INFINITY;
+                const int bk = wave_first_max(v1, v2, lane, K);
+                if (lane == 0)
+                    out.ema_best[(size_t)slot * P + p] = bk - S;
+            }
+        }
+
+        // ---- grid solve on the EMA scores over the distinct lag tuples
+        float bv = -INFINITY;
+        int bu = INT_MAX;
+        if (kp.TW == 1) {
+            // 3-4 mic grids: a thread's tuple words are loaded 8 at a time ahead of
+            // their gathers (one L2 round trip per 8 tuples, not per tuple)
+            for (int u0 = tid; u0 < kp.U; u0 += 8 * TPB) {
+                uint32_t wd[8];
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const int u = u0 + t * TPB;
+                    wd[t] = u < kp.U ? kp.tuples[u] : 0u;
+                }
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    const int u = u0 + t * TPB;
+                    if (u < kp.U) {
+                        float Lv = 0.0f;
+                        for (int p = 0; p < P; p++)
+                            Lv += E[p * K + ((wd[t] >> (8 * p)) & 0xFFu)];
+                        if (Lv > bv) {  // ascending u per thread: strict '>' keeps the first
+                            bv = Lv;
+                            bu = u;
+                        }
+                    }
+                }
+            }
+        } else {
+            for (int u = tid; u < kp.U; u += TPB) {
+                float Lv = 0.0f;
+                for (int tw = 0; tw < kp.TW; tw++) {
+                    const uint32_t word = kp.tuples[u * kp.TW + tw];
+                    for (int b = 0; b < 4; b++) {
+                        const int p = 4 * tw + b;
+                        if (p < P)
+                            Lv += E[p * K + ((word >> (8 * b)) & 0xFFu)];
+                    }
+                }
+                if (Lv > bv) {
+                    bv = Lv;
+                    bu = u;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const float ov = __shfl_xor(bv, o, 64);
+            const int ou = __shfl_xor(bu, o, 64);
+            if (ov > bv || (ov == bv && ou < bu)) {
+                bv = ov;
+                bu = ou;
+            }
+        }
+        if (lane == 0) {
+            redv[wave] = bv;
+            redi[wave] = bu;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int w = 1; w < nwaves; w++)
+                if (redv[w] > bv || (redv[w] == bv && redi[w] < bu)) {
+                    bv = redv[w];
+                    bu = redi[w];
+                }
+            if (bu < 0 || bu >= kp.U)  // NaN scores: keep the index in range
+                bu = 0;
+            const int cell = kp.tuple_cell[bu];
+            if (out.cell)
+                out.cell[slot] = cell;
+            if (max_Lf)
+                max_Lf[slot] = bv;
+            if (out.xy) {
+                const int cx = cell % kp.grid_W, cy = cell / kp.grid_W;
+                out.xy[2 * slot] = (float)(cx - kp.half_w) / kp.grid_scale;
+                out.xy[2 * slot + 1] = (float)(kp.half_h - cy) / kp.grid_scale;
+            }
+        }
+    }
+    SP_MARK(3);
+    SP_FLUSH();
+    // gated frames of this hop: one atomic per workgroup that had any
+    if (tid == 0 && ngated)
+        atomicAdd(reinterpret_cast<unsigned long long *>(sp.stats + 1), (unsigned long long)ngated);

@@ -17,6 +17,7 @@ ENGINE_DIRECT = 0
 ENGINE_GCC_PHAT = 1
 ENGINES = {"direct": ENGINE_DIRECT, "gcc_phat": ENGINE_GCC_PHAT}
 SAMPLE_FORMATS = {"adc8": 0, "pcm16": 1}  # tdoa_sample_format
+STREAM_TRIGGER_VAR_PCM16 = 131072  # TDOA_STREAM_TRIGGER_VAR_PCM16: 2 * 256^2 counts^2
 
 STATUS = {0: "TDOA_OK", -1: "TDOA_ERR_INVALID", -2: "TDOA_ERR_HIP",
           -3: "TDOA_ERR_NO_DEVICE", -4: "TDOA_ERR_NOMEM"}
@@ -30,7 +31,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_get_prior", "tdoa_dpss_q15", "tdoa_last_error", "tdoa_abi_version", "tdoa_batch_kernel",
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
-    "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f",
+    "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f", "tdoa_stream_create_pcm16",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -155,6 +156,7 @@ def load() -> C.CDLL:
     L.tdoa_heatmap.argtypes = [P, P, P, C.c_int, I64, P, P]
     L.tdoa_peaks.argtypes = [P, P, C.c_int, I64, C.POINTER(PeaksParams), C.POINTER(PeaksOutputs), P]
     L.tdoa_stream_create.argtypes = [P, I32, I32, P, I64, C.c_int, C.POINTER(P)]
+    L.tdoa_stream_create_pcm16.argtypes = [P, I32, I32, P, I64, I64, C.c_int, C.POINTER(P)]
     L.tdoa_stream_step.argtypes = [P, C.POINTER(StreamOutputs), P]
     L.tdoa_stream_reset.argtypes = [P, P]
     L.tdoa_stream_state.argtypes = [P, P, P, P, P]

@@ -12,6 +12,13 @@ A `gcc_phat` Localizer streams the GCC-PHAT engine instead (k_stream_phat):
 float scores under the localizer's weight table (set_band / set_bin_weights,
 read at every step), a float32 EMA, `out["max_Lf"]` in place of
 `out["max_L"]` and float32 `est` from state().
+
+A `gcc_phat` Localizer whose sample_format is "pcm16" streams an int16 capture
+ring [S][capture_len][M] (tdoa_stream_create_pcm16: k_stream_trigger16, then
+k_stream_phat_pcm16): the trigger of include/tdoa.h on int16 samples with the
+threshold `trigger_var` (counts^2, default 131072 = 2 * 256^2, the 8-bit
+trigger for samples scaled by 256).  The pipeline keeps the format it was
+created in.
 """
 from __future__ import annotations
 
@@ -20,7 +27,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import StreamOutputs, StreamOutputsF, check, load
+from ._lib import STREAM_TRIGGER_VAR_PCM16, StreamOutputs, StreamOutputsF, check, load
 from .localizer import Localizer
 
 
@@ -29,12 +36,19 @@ class StreamPipeline:
     # Plain stream launches are the default: 67.0 vs 71.8 us per config-5 hop
     # (tools/diag_stream_launch.py, same box; the graph's launch adds ~5 us)
     def __init__(self, loc: Localizer, capture: torch.Tensor, hop: int = 512,
-                 use_graph: bool = False):
+                 use_graph: bool = False, trigger_var: int | None = None):
         if loc.engine not in ("direct", "gcc_phat"):
             raise ValueError("the streaming pipeline runs the DIRECT or the GCC_PHAT engine")
         self.phat = loc.engine == "gcc_phat"
-        if capture.dtype != torch.uint8 or capture.dim() != 3 or capture.shape[2] != loc.dims.M:
-            raise ValueError(f"capture must be uint8 [S][T][{loc.dims.M}]")
+        # an int16 ring on a PCM16 localizer; a uint8 ring goes to tdoa_stream_create
+        # whatever the format (the library rejects it on a PCM16 context)
+        self.pcm16 = capture.dtype == torch.int16
+        if self.pcm16 and loc.sample_format != "pcm16":
+            raise ValueError("an int16 capture needs a localizer whose sample_format is \"pcm16\"")
+        if not self.pcm16 and trigger_var is not None:
+            raise ValueError("trigger_var applies to an int16 capture (the 8-bit trigger's threshold is fixed)")
+        if capture.dtype not in (torch.uint8, torch.int16) or capture.dim() != 3 or capture.shape[2] != loc.dims.M:
+            raise ValueError(f"capture must be uint8 (or, in pcm16 format, int16) [S][T][{loc.dims.M}]")
         if capture.device != loc.torch_device or not capture.is_contiguous():
             raise ValueError("capture must be contiguous on the localizer's device")
         self.loc, self.capture, self.hop = loc, capture, hop
@@ -61,9 +75,17 @@ class StreamPipeline:
         # graph capture needs a real (non-default) stream
         self.stream = torch.cuda.Stream(device=dev)
         h = C.c_void_p()
-        check(load().tdoa_stream_create(loc._ctx, S, hop, C.c_void_p(capture.data_ptr()),
-                                        self.capture_len, int(use_graph), C.byref(h)),
-              "tdoa_stream_create")
+        if self.pcm16:
+            self.trigger_var = STREAM_TRIGGER_VAR_PCM16 if trigger_var is None else int(trigger_var)
+            if not -2 ** 63 <= self.trigger_var < 2 ** 63:
+                raise ValueError("trigger_var does not fit int64")
+            check(load().tdoa_stream_create_pcm16(loc._ctx, S, hop, C.c_void_p(capture.data_ptr()),
+                                                  self.capture_len, self.trigger_var, int(use_graph),
+                                                  C.byref(h)), "tdoa_stream_create_pcm16")
+        else:
+            check(load().tdoa_stream_create(loc._ctx, S, hop, C.c_void_p(capture.data_ptr()),
+                                            self.capture_len, int(use_graph), C.byref(h)),
+                  "tdoa_stream_create")
         self._h = h
 
     def step(self) -> dict:

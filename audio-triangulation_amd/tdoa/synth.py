@@ -204,6 +204,52 @@ def adc_stream(S: int, T: int, M: int, lut: np.ndarray, max_shift: int, seed: in
     return b.permute(0, 2, 1).contiguous()
 
 
+def pcm16_stream(S: int, T: int, M: int, lut: np.ndarray, max_shift: int, seed: int,
+                 device: str | torch.device = "cpu", burst_len: int = 700,
+                 gap: tuple = (1500, 3500), src_std: float = 3000.0, noise_std: float = 30.0,
+                 dc=None) -> torch.Tensor:
+    """adc_stream's burst scenario as 16-bit PCM: int16 [S][T][M] on `device`.
+
+    Each stream has a stationary source at a random grid cell emitting
+    N(0, src_std) bursts of `burst_len` samples separated by random gaps; mic m
+    hears it delayed by tau_m (tau_0 = 0, tau_m = LUT_(0,m)[cell] - max_shift)
+    over N(0, noise_std) noise, plus the offset dc[m] counts (default 0; one
+    per mic, shared by the streams), rounded and clipped to int16.
+    Draw order (numpy default_rng(seed)): cells [S]; gaps [S][nb] uniform over
+    [gap[0], gap[1]) with nb = (T + 2 pad) // gap[0] + 2 and pad = max_shift + 1;
+    the first burst's start [S] uniform over [0, gap[0]); source [S][T + 2 pad];
+    noise [S][M][T].  Burst b of a stream starts at first + gaps[:b].sum() on
+    the source's own time axis, which is the capture's shifted by pad."""
+    rng = np.random.default_rng(int(seed))
+    P = lut.shape[0]
+    lut2 = np.asarray(lut).reshape(P, -1).astype(np.int64)
+    cells = rng.integers(0, lut2.shape[1], S)
+    tau = np.zeros((S, M), np.int64)
+    for m in range(1, M):
+        tau[:, m] = lut2[m - 1][cells] - max_shift  # pair (0, m) is index m-1
+    pad = max_shift + 1
+    TT = T + 2 * pad
+    nb = TT // gap[0] + 2
+    gaps = rng.integers(gap[0], gap[1], (S, nb))
+    first = rng.integers(0, gap[0], S)
+    starts = first[:, None] + np.cumsum(gaps, 1) - gaps
+    env = np.zeros((S, TT + 1), np.int32)
+    for s in range(S):
+        st = starts[s][starts[s] < TT]
+        np.add.at(env[s], st, 1)
+        np.add.at(env[s], np.minimum(st + burst_len, TT), -1)
+    env = np.cumsum(env, 1)[:, :TT] > 0
+    y = rng.standard_normal((S, TT)) * float(src_std) * env
+    x = rng.standard_normal((S, M, T)) * float(noise_std)
+    off = np.zeros(M) if dc is None else np.asarray(dc, np.float64)[:M]
+    assert off.size == M, "one offset per mic"
+    t = np.arange(T)
+    for m in range(M):
+        x[:, m] += np.take_along_axis(y, pad + t[None, :] - tau[:, m:m + 1], 1) + off[m]
+    cap = np.clip(np.rint(x), -32768, 32767).astype(np.int16).transpose(0, 2, 1)
+    return torch.from_numpy(np.ascontiguousarray(cap)).to(torch.device(device))
+
+
 def square_mics(side: float = 0.15) -> np.ndarray:
     """Config 3: 4-mic square centred on the origin."""
     h = side / 2

@@ -291,10 +291,11 @@ typedef enum tdoa_sample_format {
  * kernel is fused but whose PCM16 route has two passes gets the spectrum
  * scratch (128 MiB, freed by tdoa_destroy) on first need, as
  * tdoa_set_bin_weights does.  tdoa_correlate_prepared and the per-frame
- * reference symbols run the integer path whatever the format;
- * tdoa_stream_create on a PCM16 context is TDOA_ERR_INVALID (the capture ring
- * is 8-bit by definition), and a pipeline created before the switch keeps its
- * 8-bit parameters. */
+ * reference symbols run the integer path whatever the format.  A streaming
+ * pipeline takes its format at creation and keeps it whatever the context is
+ * switched to afterwards: tdoa_stream_create takes 8-bit capture rings and is
+ * TDOA_ERR_INVALID on a PCM16 context, tdoa_stream_create_pcm16 (below) takes
+ * int16 rings and is TDOA_ERR_INVALID on an ADC8 one. */
 int tdoa_set_sample_format(tdoa_ctx *ctx, int format);
 int tdoa_get_sample_format(const tdoa_ctx *ctx, int *format);
 
@@ -376,6 +377,48 @@ typedef struct tdoa_stream_outputs_f { /* the same for a GCC_PHAT pipeline */
 int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
                        const uint8_t *capture, int64_t capture_len, int use_graph,
                        tdoa_stream **out);
+
+/* ---- Streaming 16-bit PCM capture rings (GCC_PHAT in TDOA_SAMPLES_PCM16) ----
+ * capture[S][capture_len][M] holds int16 samples (2-byte aligned; a stream's
+ * ring starts at s * capture_len * M * 2 bytes).  The trigger is the one above
+ * on int16 samples with a caller-supplied threshold.  For stream s, samples
+ * x_m[t] (zero for t < 0), h = N/2, pos the samples consumed before the hop:
+ *   a candidate end e lies in (pos, pos + hop] and is eligible iff
+ *   e - ring_start[s] >= N;  older half O = [e-N, e-h), newer half I = [e-h, e);
+ *   pw(m, R) = h * sum_R x_m^2 - (sum_R x_m)^2, exact in int64;
+ *   the stream fires iff sum_m pw(m, O) > trigger_var * h^2 + sum_m pw(m, I);
+ *   the first eligible firing e of the hop is taken, then ring_start[s] = e
+ *   (ring_start starts at 0).
+ * The 8-bit trigger is this rule with trigger_var = 2.  trigger_var is in
+ * counts^2, in [0, 2^30]; with TDOA_STREAM_TRIGGER_VAR_PCM16 = 2 * 256^2 a ring
+ * holding (u8 - 128) * 256 fires exactly where the 8-bit ring does (both sides
+ * scale by 65536 and a DC shift cancels in pw).
+ * Int64 bounds over every accepted shape (|x| <= 2^15, h <= 2048, M <= 8):
+ * |sum_R x| <= h 2^15 = 2^26, so (sum_R x)^2 <= 2^52; sum_R x^2 <= h 2^30 and
+ * h * sum_R x^2 <= 2^52; 0 <= pw <= 2^52 (Cauchy-Schwarz), over 8 mics each
+ * side's sum <= 2^55; trigger_var * h^2 <= 2^30 * 2^22 = 2^52; the kernel's
+ * prefix sums of x over the N + hop - 1 <= 8191 samples it reads stay below
+ * 2^28 < 2^31 (int32) and those of x^2 below 2^43.
+ * Each triggered frame x[e-N, e) goes through the PCM16 front end as defined
+ * above (off = floor(mean), y = x - off, s = (y W) >> 15) and from there on
+ * through what a GCC_PHAT pipeline does with an 8-bit frame: PHAT with
+ * phat_eps, the context's bin-weight table read at every step, the inverses,
+ * first maximum, prior, gate, the float EMA on gated frames with
+ * now_us = e * 1e6 / fs, and the grid solve on the EMA scores.
+ * The result is an ordinary tdoa_stream: it steps with tdoa_stream_step_f, is
+ * read with tdoa_stream_state_f (and tdoa_stream_state with est = NULL), and
+ * tdoa_stream_reset / tdoa_stream_destroy apply; graph mode and plain stream
+ * launches both work.  Kernels: k_stream_trigger16, k_stream_phat_pcm16.
+ * TDOA_ERR_INVALID, with tdoa_last_error naming the cause: a DIRECT context; a
+ * GCC_PHAT context in ADC8 format; trigger_var outside [0, 2^30]; hop outside
+ * [1, N]; capture_len < N + 2 hop; a shape outside the GCC_PHAT LDS rule above
+ * or whose trigger needs more than 150 KiB of LDS
+ * (2 M (N + hop - 1) + 12 (N + hop) bytes). */
+#define TDOA_STREAM_TRIGGER_VAR_PCM16 131072 /* 2 * 256^2: the 8-bit threshold for samples scaled by 256 */
+int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
+                             const int16_t *capture /* device [S][capture_len][M] */,
+                             int64_t capture_len, int64_t trigger_var, int use_graph,
+                             tdoa_stream **out);
 /* One hop for every stream, asynchronous on `stream` (graph mode needs a
  * non-NULL stream; the captured graph is reused while `out` and `stream`
  * stay the same). */

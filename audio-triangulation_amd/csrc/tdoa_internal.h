@@ -184,6 +184,12 @@ int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *st
 // the trigger on an int16 ring (k_stream_trigger16; sp.capture holds int16):
 // thr = trigger_var * (N/2)^2; firing streams are listed only (by_id form)
 int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_t thr, void *stream);
+// continuous mode's frame lister in place of a trigger (k_stream_active<T, M>,
+// T = int16_t for pcm16 else uint8_t): every stream whose frame [e - N, e),
+// e = pos + H >= N, has sum_m (N sum x_m^2 - (sum x_m)^2) >= thr, with
+// thr = activity_var * N^2; listed in the by_id form (ids, end, ring_at);
+// ring_start is not touched
+int tdoa_launch_stream_active(const tdoa_stream_params &sp, int64_t S, int64_t thr, bool pcm16, void *stream);
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,
                               const tdoa_stream_kout &out, int64_t S, void *stream);
 // the GCC_PHAT hop after the trigger (tdoa_stream_phat.hip, k_stream_phat):

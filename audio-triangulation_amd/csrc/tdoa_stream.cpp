@@ -9,7 +9,9 @@
 // A GCC_PHAT pipeline runs the same trigger, then k_stream_phat
 // (tdoa_stream_phat.hip): float scores, float EMA state, max_Lf.  On an int16
 // ring (tdoa_stream_create_pcm16) it runs k_stream_trigger16, then
-// k_stream_phat_pcm16.
+// k_stream_phat_pcm16.  A continuous pipeline (tdoa_stream_create_continuous)
+// runs k_stream_active in place of either trigger -- one candidate frame per
+// stream and hop behind an activity threshold -- then the same k_stream_phat*.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -66,6 +68,8 @@ struct tdoa_stream {
     bool pcm16 = false;     // int16 capture ring (tdoa_stream_create_pcm16): k_stream_trigger16,
                             // k_stream_phat_pcm16; the format is the pipeline's from creation on
     int64_t trig_thr = 0;   // ... its trigger threshold, trigger_var * (N/2)^2
+    bool continuous = false;  // tdoa_stream_create_continuous: k_stream_active lists the frames, no trigger
+    int64_t act_thr = 0;      // ... its threshold, activity_var * N^2
 };
 
 namespace {
@@ -93,8 +97,14 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
     sp.count = st->sp.count + par;
     sp.count_next = st->sp.count + (1 - par);
     bool by_id = false;  // where DIRECT finds the frames: the capture ring or compact copies
-    int rc = st->pcm16 ? tdoa_launch_stream_trigger16(sp, st->S, st->trig_thr, s)
+    int rc;
+    if (st->continuous) {
+        rc = tdoa_launch_stream_active(sp, st->S, st->act_thr, st->pcm16, s);
+        by_id = true;  // listed only: k_stream_phat stages each frame from its stream's ring
+    } else {
+        rc = st->pcm16 ? tdoa_launch_stream_trigger16(sp, st->S, st->trig_thr, s)
                        : tdoa_launch_stream_trigger(sp, st->S, s, &by_id);
+    }
     if (rc)
         return rc;
     if (st->phat) {
@@ -140,21 +150,34 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
     return tdoa_launch_stream_update(sp, st->kp, to_kout(out), st->S, s);
 }
 
-// tdoa_stream_create (pcm16 false: `capture` holds bytes) and
-// tdoa_stream_create_pcm16 (int16 samples, GCC_PHAT in PCM16 format only)
+// tdoa_stream_create (pcm16 false: `capture` holds bytes),
+// tdoa_stream_create_pcm16 (int16 samples, GCC_PHAT in PCM16 format only) and
+// tdoa_stream_create_continuous (GCC_PHAT only; the ring's type is the
+// context's sample format, `pcm16` is not read; `var` is activity_var)
 int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t hop, const void *capture,
-                  int64_t capture_len, bool pcm16, int64_t trigger_var, int use_graph, tdoa_stream **out)
+                  int64_t capture_len, bool pcm16, int64_t var, int use_graph, tdoa_stream **out,
+                  bool continuous = false)
 {
     if (!ctx || !out || !capture)
         return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument", fn);
     *out = nullptr;
     const int engine = tdoa_ctx_engine(ctx);
+    if (continuous && engine != TDOA_ENGINE_GCC_PHAT)
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: continuous mode needs a GCC_PHAT context (DIRECT reproduces the "
+                                           "firmware, which has no such mode)", fn);
     if (engine != TDOA_ENGINE_DIRECT && engine != TDOA_ENGINE_GCC_PHAT)
         return tdoa_fail(TDOA_ERR_INVALID, "%s: needs a DIRECT or GCC_PHAT context", fn);
     const bool phat = engine == TDOA_ENGINE_GCC_PHAT;
     const tdoa_kparams &kp = *tdoa_ctx_kparams(ctx);
     const int M = kp.M, N = kp.N, P = kp.P, K = kp.K;
-    if (pcm16) {
+    const int64_t trigger_var = var;
+    if (continuous) {
+        pcm16 = kp.pcm16 != 0;
+        if (var < 0 || var > ((int64_t)1 << 30))
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: activity_var %lld outside [0, 2^30]", fn, (long long)var);
+        if (pcm16 && ((uintptr_t)capture & 1) != 0)
+            return tdoa_fail(TDOA_ERR_INVALID, "%s: capture is not 2-byte aligned", fn);
+    } else if (pcm16) {
         if (!phat)
             return tdoa_fail(TDOA_ERR_INVALID, "%s: an int16 capture ring needs a GCC_PHAT context (DIRECT stays 8-bit)",
                              fn);
@@ -180,7 +203,7 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
         return tdoa_fail(TDOA_ERR_INVALID, "%s: hop %d outside [1, frame_len]", fn, hop);
     if (capture_len < (int64_t)N + 2 * hop)
         return tdoa_fail(TDOA_ERR_INVALID, "%s: capture_len %lld < frame_len + 2 hop", fn, (long long)capture_len);
-    if (tdoa_stream_trigger_lds(M, N, hop) > 150 * 1024)
+    if (!continuous && tdoa_stream_trigger_lds(M, N, hop) > 150 * 1024)  // no trigger runs in continuous mode
         return tdoa_fail(TDOA_ERR_INVALID, "%s: (frame_len + hop) x mics too large", fn);
     const int dev = tdoa_ctx_device(ctx);
     HIP_TRY(hipSetDevice(dev));
@@ -193,7 +216,9 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->use_graph = use_graph;
     st->phat = phat;
     st->pcm16 = pcm16;
-    st->trig_thr = pcm16 ? trigger_var * (int64_t)(N / 2) * (N / 2) : 0;  // <= 2^30 * 2^22
+    st->trig_thr = pcm16 && !continuous ? trigger_var * (int64_t)(N / 2) * (N / 2) : 0;  // <= 2^30 * 2^22
+    st->continuous = continuous;
+    st->act_thr = continuous ? var * (int64_t)N * N : 0;  // <= 2^30 * 2^24
     if (phat) {
         st->phat_eps = tdoa_ctx_phat_eps(ctx);
         // TDOA_STREAM_PHAT_GRID=n caps k_stream_phat's launch size (A/B runs)
@@ -210,7 +235,7 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     };
     // (a GCC_PHAT pipeline keeps the frame's scores on chip: no fresh* buffers, float EMA state)
     const size_t o_pos = take(8), o_count = take(8), o_rs = take(S * 8), o_ids = take(S * 4),
-                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(pcm16 ? 0 : S * M * N),
+                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(pcm16 || continuous ? 0 : S * M * N),
                  o_fresh = take(phat ? 0 : S * P * K * 8), o_fl = take(phat ? 0 : S * P * 4),
                  o_fg = take(phat ? 0 : S), o_est = take(S * P * K * (phat ? 4 : 8)), o_last = take(S * 8),
                  o_stats = take(16);
@@ -231,7 +256,7 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.ids = (int32_t *)(b + o_ids);
     sp.end = (int64_t *)(b + o_end);
     sp.ring_at = (int64_t *)(b + o_at);
-    sp.frames = pcm16 ? nullptr : (int16_t *)(b + o_frames);
+    sp.frames = pcm16 || continuous ? nullptr : (int16_t *)(b + o_frames);  // the compact-copy trigger's only
     sp.fresh = phat ? nullptr : (int64_t *)(b + o_fresh);
     sp.fresh_lags = phat ? nullptr : (int32_t *)(b + o_fl);
     sp.fresh_gate = phat ? nullptr : (uint8_t *)(b + o_fg);
@@ -260,6 +285,14 @@ extern "C" int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int3
 {
     return stream_create("tdoa_stream_create_pcm16", ctx, num_streams, hop, capture, capture_len, true, trigger_var,
                          use_graph, out);
+}
+
+extern "C" int tdoa_stream_create_continuous(tdoa_ctx *ctx, int32_t num_streams, int32_t hop, const void *capture,
+                                             int64_t capture_len, int64_t activity_var, int use_graph,
+                                             tdoa_stream **out)
+{
+    return stream_create("tdoa_stream_create_continuous", ctx, num_streams, hop, capture, capture_len, false,
+                         activity_var, use_graph, out, true);
 }
 
 namespace {

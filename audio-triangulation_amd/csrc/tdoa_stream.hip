@@ -21,6 +21,10 @@
 //                     (clock now_us = end * 1e6 / fs) and the grid solve on
 //                     the EMA scores (vga_heatmap.h:99-108 runs on corr_*);
 //                     advances the device sample clock by H.
+// A GCC_PHAT pipeline runs k_stream_phat (tdoa_stream_phat.hip) after the
+// trigger -- k_stream_trigger16 on an int16 ring -- or, in continuous mode,
+// after k_stream_active, which lists one candidate frame per stream and hop
+// behind an activity threshold instead of triggering.
 //
 // Built with -ffp-contract=off: the EMA's float steps round as the
 // reference's IEEE host build does.
@@ -29,6 +33,7 @@
 
 #include <climits>
 #include <cstdlib>
+#include <type_traits>
 
 #include "tdoa_internal.h"
 #include "tdoa_keys.h"
@@ -659,6 +664,194 @@ __global__ void __launch_bounds__(64 * TRIG_NWB) k_stream_trigger_p(tdoa_stream_
     }
 }
 
+// ------------------------------------------- the activity gate (continuous mode)
+// tdoa_stream_create_continuous (include/tdoa.h): one candidate per stream and
+// hop, e = pos + H, eligible iff e >= N; the frame F = [e - N, e) is listed iff
+//     sum_m (N sum_F x_m^2 - (sum_F x_m)^2) >= thr        (thr = activity_var N^2)
+// on the ring's own sample values (T = uint8_t or int16_t), exact in int64:
+// sum x^2 <= 2^42 and |sum x| <= 2^27 at |x| <= 2^15, N <= 4096, so both terms
+// stay within 2^54 per mic and 2^57 over 8 mics.
+//
+// One wave per stream, ACT_NWB streams per workgroup, persistent; sums in
+// registers, no LDS staging.  The frame is N M contiguous ring elements from
+// ((e - N) mod capture_len) M, wrapping at most once, read as 16-byte vectors of
+// V = 16 / sizeof(T) elements: vector vi = k0 + 64 c + lane (c < M, k0 a
+// multiple of 64 M) holds elements vi V + v, whose mic is
+//     (vi V + v) mod M = (q + rho) mod M,  q = (64 c V + v) mod M,  rho = (lane V) mod M
+// -- q is a compile-time register index, rho a per-lane rotation undone once
+// per stream (none when M divides V).  The M vectors of a group are requested
+// before the first is used.  A vector is one 16-byte load where it lies inside
+// the ring and its address is 16-byte aligned -- decided per vector from the
+// actual address: a stream's ring may start 1-byte (u8) or 2-byte (int16)
+// aligned only, when capture_len M is odd -- and V element loads with the wrap
+// otherwise.  A lane's sum x^2 is 32-bit over at most two int16 samples
+// ((-32768)^2 * 4 = 2^32) and 64-bit from there; u8 sums fit 32 bits
+// (4096 * 8 * 255^2 < 2^31).  The M sums of x and the sum of x^2 are
+// wave-scanned (DPP; the 64-bit one as its low 20 bits and the rest: each
+// part's wave total stays below 2^26), the test is wave-uniform, and the
+// workgroup's listed streams take their slots with one atomic, as
+// k_stream_trigger_p's do.  Sixteen waves per workgroup: a hop's slot atomics
+// all hit one word, about 9 ns each at config 5 -- with four waves per
+// workgroup the 2048 of them were half the kernel's 27 us (13.3 us with 512).
+// Requesting the next stream's vectors ahead of the sums measured slower.
+constexpr int ACT_NWB = 16;  // waves (streams in flight) per workgroup
+
+template <typename T>
+__device__ __forceinline__ uint4 active_load(const T *ring, int64_t r, int64_t R)
+{
+    constexpr int V = 16 / sizeof(T), PW = 4 / sizeof(T);  // elements per vector, per dword
+    typedef typename std::make_unsigned<T>::type UT;
+    if (r >= R)
+        r -= R;
+    const T *p = ring + r;
+    if (r + V <= R && ((uintptr_t)p & 15u) == 0)
+        return *reinterpret_cast<const uint4 *>(p);
+    uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int v = 0; v < V; v++) {
+        int64_t j = r + v;
+        if (j >= R)
+            j -= R;
+        d[v / PW] |= (uint32_t)(UT)ring[j] << (8 * sizeof(T) * (v % PW));
+    }
+    return uint4{d[0], d[1], d[2], d[3]};
+}
+
+template <typename T, int M>
+__global__ void __launch_bounds__(64 * ACT_NWB) k_stream_active(tdoa_stream_params sp, int64_t S, long long thr)
+{
+    constexpr int V = 16 / sizeof(T), NWB = ACT_NWB;
+    constexpr bool ROT = V % M != 0;  // a lane's vectors start at a mic that depends on the lane
+    __shared__ int nlisted[NWB], slot_base;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && sp.count_next)
+        *sp.count_next = 0;  // the next hop's counter (last read by the previous hop)
+    const int N = sp.N;
+    const int64_t e = *sp.pos + sp.H;  // the hop's one candidate end
+    if (e < N)
+        return;  // every stream alike: a frame would reach before the stream's start
+    const int64_t cl = sp.capture_len, R = cl * M;
+    const int64_t at = (e - N) % cl, b0 = at * M;  // b0 + N M <= 2 R: N <= cl
+    const int NV = N * M / V;  // whole vectors: N is a multiple of 16
+    const int rho = (lane * V) % M;
+    const T *cap = reinterpret_cast<const T *>(sp.capture);
+    // this wave's listed streams: lane i holds the i-th
+    int my_n = 0, my_id = 0;
+    int a1[M];          // sum x of mic (q + rho) mod M
+    uint64_t a2 = 0;    // sum x^2 over all mics
+    uint32_t a2w = 0;   // ... of a u8 ring
+#pragma unroll
+    for (int q = 0; q < M; q++)
+        a1[q] = 0;
+    // vectors k0 + 64 c + lane (c < M) of stream s's frame, all requested before any is used
+    auto fetch = [&](int64_t s, int k0, uint4(&x)[M]) __attribute__((always_inline)) {
+        const T *ring = cap + (size_t)s * R;
+#pragma unroll
+        for (int c = 0; c < M; c++) {
+            const int vi = k0 + 64 * c + lane;
+            x[c] = vi < NV ? active_load<T>(ring, b0 + (int64_t)vi * V, R) : uint4{0u, 0u, 0u, 0u};
+        }
+    };
+    auto accumulate = [&](const uint4(&x)[M]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < M; c++) {
+            const uint32_t w[4] = {x[c].x, x[c].y, x[c].z, x[c].w};
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if constexpr (sizeof(T) == 1) {
+                    // per mic a v_dot4 with the 0/1 mask of its bytes, the squares a v_dot4 of the word with itself
+#pragma unroll
+                    for (int q = 0; q < M; q++) {
+                        uint32_t mask = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; b++)
+                            mask |= ((64 * c * V + 4 * j + b) % M == q ? 1u : 0u) << (8 * b);
+                        if (mask)
+                            a1[q] = (int)__builtin_amdgcn_udot4(w[j], mask, (uint32_t)a1[q], false);
+                    }
+                    a2w = __builtin_amdgcn_udot4(w[j], w[j], a2w, false);
+                } else {
+                    const int lo = (int)(int16_t)(w[j] & 0xFFFFu), hi = (int)w[j] >> 16;
+                    a1[(64 * c * V + 2 * j) % M] += lo;
+                    a1[(64 * c * V + 2 * j + 1) % M] += hi;
+                    a2 += (uint32_t)(lo * lo) + (uint32_t)(hi * hi);  // <= 2^31: two samples in 32 bits
+                }
+            }
+        }
+    };
+    // stream s's sums are complete: the test, the listing, the sums cleared
+    auto finish = [&](int64_t s) __attribute__((always_inline)) {
+        if constexpr (sizeof(T) == 1)
+            a2 = a2w;
+        // r[m]: sum x of mic m; r[M], r[M + 1]: sum x^2 as its low 20 bits and the rest
+        int r[M + 2];
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            if constexpr (ROT) {
+                const int q = m - rho < 0 ? m - rho + M : m - rho;
+                int v = a1[0];
+#pragma unroll
+                for (int k = 1; k < M; k++)
+                    v = q == k ? a1[k] : v;
+                r[m] = v;
+            } else {
+                r[m] = a1[m];
+            }
+        }
+        r[M] = (int)(a2 & 0xFFFFFu);
+        r[M + 1] = (int)(a2 >> 20);  // a lane's sum x^2 <= 512 * 2^30
+        wave_scan_incl_n(r);
+        long long sq = 0;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const long long t = __builtin_amdgcn_readlane(r[m], 63);
+            sq += t * t;
+        }
+        const long long s2 = ((long long)__builtin_amdgcn_readlane(r[M + 1], 63) << 20) +
+                             (long long)__builtin_amdgcn_readlane(r[M], 63);
+        if ((long long)N * s2 - sq >= thr) {  // wave-uniform
+            if (lane == my_n)
+                my_id = (int)s;
+            ++my_n;
+        }
+#pragma unroll
+        for (int q = 0; q < M; q++)
+            a1[q] = 0;
+        a2 = 0;
+        a2w = 0;
+    };
+    const int64_t GW = (int64_t)gridDim.x * NWB;
+    for (int64_t s = (int64_t)blockIdx.x * NWB + wv; s < S; s += GW) {
+        for (int k0 = 0; k0 < NV; k0 += 64 * M) {
+            uint4 x[M];
+            fetch(s, k0, x);
+            accumulate(x);
+        }
+        finish(s);
+    }
+    // the workgroup's listed streams into the compact list: one atomic
+    if (lane == 0)
+        nlisted[wv] = my_n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int w = 0; w < NWB; w++)
+            n += nlisted[w];
+        slot_base = n ? atomicAdd(sp.count, n) : 0;
+    }
+    __syncthreads();
+    int o = slot_base;
+    for (int w = 0; w < wv; w++)
+        o += nlisted[w];
+    // o + lane < S holds while the hop's slot started at 0 (one slot per listed
+    // stream); the clamp keeps a corrupted counter from writing past S
+    if (lane < my_n && o + lane < S) {
+        sp.ids[o + lane] = my_id;
+        sp.end[o + lane] = e;
+        sp.ring_at[o + lane] = at;
+    }
+}
+
 // correlations.c:40-43 in the reference's float/double steps
 __device__ __forceinline__ float decay_us(uint64_t now, uint64_t last) { return tdoa_decay_dev(now, last); }
 
@@ -922,6 +1115,44 @@ int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_
     hipLaunchKernelGGL(k_stream_trigger16, dim3((unsigned)S), dim3(TPB), lds, (hipStream_t)stream, sp, (long long)thr);
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger16 launch");
+}
+
+template <typename T, int M>
+static void launch_active(const tdoa_stream_params &sp, int64_t S, int64_t thr, hipStream_t st)
+{
+    const int res = tdoa_resident_blocks((const void *)k_stream_active<T, M>, 64 * ACT_NWB, 0);
+    int64_t grid = (S + ACT_NWB - 1) / ACT_NWB;
+    if (res > 0 && grid > res)
+        grid = res;
+    // a wave lists at most 64 streams (one per lane)
+    const int64_t min_grid = (S + ACT_NWB * 64 - 1) / (ACT_NWB * 64);
+    if (grid < min_grid)
+        grid = min_grid;
+    hipLaunchKernelGGL((k_stream_active<T, M>), dim3((unsigned)grid), dim3(64 * ACT_NWB), 0, st, sp, S, (long long)thr);
+}
+
+template <typename T>
+static bool launch_active_m(const tdoa_stream_params &sp, int64_t S, int64_t thr, hipStream_t st)
+{
+    switch (sp.M) {
+    case 2: launch_active<T, 2>(sp, S, thr, st); return true;
+    case 3: launch_active<T, 3>(sp, S, thr, st); return true;
+    case 4: launch_active<T, 4>(sp, S, thr, st); return true;
+    case 5: launch_active<T, 5>(sp, S, thr, st); return true;
+    case 6: launch_active<T, 6>(sp, S, thr, st); return true;
+    case 7: launch_active<T, 7>(sp, S, thr, st); return true;
+    case 8: launch_active<T, 8>(sp, S, thr, st); return true;
+    default: return false;
+    }
+}
+
+int tdoa_launch_stream_active(const tdoa_stream_params &sp, int64_t S, int64_t thr, bool pcm16, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (!(pcm16 ? launch_active_m<int16_t>(sp, S, thr, st) : launch_active_m<uint8_t>(sp, S, thr, st)))
+        return tdoa_set_error(-1, "stream: the activity gate takes 2 to 8 mics");
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_active launch");
 }
 
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,

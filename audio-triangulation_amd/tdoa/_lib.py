@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f", "tdoa_stream_create_pcm16",
+    "tdoa_stream_create_continuous",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -157,6 +158,7 @@ def load() -> C.CDLL:
     L.tdoa_peaks.argtypes = [P, P, C.c_int, I64, C.POINTER(PeaksParams), C.POINTER(PeaksOutputs), P]
     L.tdoa_stream_create.argtypes = [P, I32, I32, P, I64, C.c_int, C.POINTER(P)]
     L.tdoa_stream_create_pcm16.argtypes = [P, I32, I32, P, I64, I64, C.c_int, C.POINTER(P)]
+    L.tdoa_stream_create_continuous.argtypes = [P, I32, I32, P, I64, I64, C.c_int, C.POINTER(P)]
     L.tdoa_stream_step.argtypes = [P, C.POINTER(StreamOutputs), P]
     L.tdoa_stream_reset.argtypes = [P, P]
     L.tdoa_stream_state.argtypes = [P, P, P, P, P]

@@ -19,6 +19,17 @@ k_stream_phat_pcm16): the trigger of include/tdoa.h on int16 samples with the
 threshold `trigger_var` (counts^2, default 131072 = 2 * 256^2, the 8-bit
 trigger for samples scaled by 256).  The pipeline keeps the format it was
 created in.
+
+mode="continuous" (a `gcc_phat` Localizer; tdoa_stream_create_continuous:
+k_stream_active in place of a trigger) chooses frames for continuous audio
+instead of clicks.  The ring is uint8 or int16 according to loc.sample_format.
+With pos the samples consumed before the hop there is one candidate per stream
+and hop, e = pos + hop, eligible iff e >= N; its frame is F = [e - N, e);
+pw(m) = N * sum_F x_m^2 - (sum_F x_m)^2 on the ring's own sample values, exact
+in int64; the stream is listed iff sum_m pw(m) >= activity_var * N^2.  The
+comparison is >=, so activity_var = 0 (the default) lists every eligible
+stream; activity_var is in counts^2 summed over mics, in [0, 2^30].  Listed
+frames go through what triggered frames do, the gate sum lag^2 > 4 included.
 """
 from __future__ import annotations
 
@@ -36,10 +47,25 @@ class StreamPipeline:
     # Plain stream launches are the default: 67.0 vs 71.8 us per config-5 hop
     # (tools/diag_stream_launch.py, same box; the graph's launch adds ~5 us)
     def __init__(self, loc: Localizer, capture: torch.Tensor, hop: int = 512,
-                 use_graph: bool = False, trigger_var: int | None = None):
+                 use_graph: bool = False, trigger_var: int | None = None, mode: str = "triggered",
+                 activity_var: int | None = None):
         if loc.engine not in ("direct", "gcc_phat"):
             raise ValueError("the streaming pipeline runs the DIRECT or the GCC_PHAT engine")
+        if mode not in ("triggered", "continuous"):
+            raise ValueError(f"mode must be \"triggered\" or \"continuous\", not {mode!r}")
+        self.mode = mode
+        self.activity_var = None
         self.phat = loc.engine == "gcc_phat"
+        if mode == "continuous":
+            if not self.phat:
+                raise ValueError("continuous mode needs a gcc_phat localizer (DIRECT reproduces the firmware)")
+            if trigger_var is not None:
+                raise ValueError("trigger_var applies to triggered mode; continuous mode takes activity_var")
+            want = torch.int16 if loc.sample_format == "pcm16" else torch.uint8
+            if capture.dtype != want:
+                raise ValueError(f"continuous mode on a {loc.sample_format} localizer takes a {want} capture")
+        elif activity_var is not None:
+            raise ValueError("activity_var applies to mode=\"continuous\"")
         # an int16 ring on a PCM16 localizer; a uint8 ring goes to tdoa_stream_create
         # whatever the format (the library rejects it on a PCM16 context)
         self.pcm16 = capture.dtype == torch.int16
@@ -75,7 +101,14 @@ class StreamPipeline:
         # graph capture needs a real (non-default) stream
         self.stream = torch.cuda.Stream(device=dev)
         h = C.c_void_p()
-        if self.pcm16:
+        if mode == "continuous":
+            self.activity_var = 0 if activity_var is None else int(activity_var)
+            if not -2 ** 63 <= self.activity_var < 2 ** 63:
+                raise ValueError("activity_var does not fit int64")
+            check(load().tdoa_stream_create_continuous(loc._ctx, S, hop, C.c_void_p(capture.data_ptr()),
+                                                       self.capture_len, self.activity_var, int(use_graph),
+                                                       C.byref(h)), "tdoa_stream_create_continuous")
+        elif self.pcm16:
             self.trigger_var = STREAM_TRIGGER_VAR_PCM16 if trigger_var is None else int(trigger_var)
             if not -2 ** 63 <= self.trigger_var < 2 ** 63:
                 raise ValueError("trigger_var does not fit int64")

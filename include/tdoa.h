@@ -419,6 +419,50 @@ int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
                              const int16_t *capture /* device [S][capture_len][M] */,
                              int64_t capture_len, int64_t trigger_var, int use_graph,
                              tdoa_stream **out);
+
+/* ---- Continuous streaming: a frame per hop behind an activity gate ----
+ * A second way of choosing frames, for rings that carry continuous audio
+ * (speech, a motor) where the click trigger above fires at chance positions or
+ * not at all.  GCC_PHAT contexts only.  The ring's element type follows the
+ * context's sample format at creation: capture[S][capture_len][M] holds uint8_t
+ * for TDOA_SAMPLES_ADC8 and int16_t (2-byte aligned) for TDOA_SAMPLES_PCM16;
+ * the pipeline keeps that format whatever the context is switched to afterwards.
+ * For stream s with samples x_m[t], pos the samples consumed before the hop:
+ *   one candidate per stream and hop, e = pos + hop, eligible iff e >= N (a
+ *   frame never reaches before the stream's start);  the frame is F = [e-N, e);
+ *   pw(m) = N * sum_F x_m^2 - (sum_F x_m)^2 on the ring's own sample values
+ *   (u8 counts 0..255 or int16 counts), exact in int64;
+ *   the stream is listed iff sum_m pw(m) >= activity_var * N^2.
+ * The comparison is >=: activity_var = 0 lists every eligible stream (one frame
+ * per stream and hop).  activity_var is in counts^2 of the ring's samples,
+ * summed over mics, in [0, 2^30] -- trigger_var's convention: the frame's sample
+ * variance summed over the mics.  ring_start is neither read nor written.
+ * Int64 bounds over every accepted shape (|x| <= 2^15, N <= 4096, M <= 8):
+ * sum_F x^2 <= N 2^30 = 2^42, so N * sum_F x^2 <= 2^54; |sum_F x| <= N 2^15 =
+ * 2^27, so (sum_F x)^2 <= 2^54; 0 <= pw <= 2^54 (Cauchy-Schwarz), over 8 mics
+ * the sum <= 2^57; activity_var * N^2 <= 2^30 * 2^24 = 2^54.  The kernel holds a
+ * lane's partial sum of x^2 in 32 bits over at most two samples
+ * ((-32768)^2 * 4 = 2^32 does not fit) and in 64 bits from there.
+ * Each listed frame goes through exactly what a triggered frame does
+ * (k_stream_phat staging it from the ring, or k_stream_phat_pcm16 with the
+ * PCM16 front end): PHAT with phat_eps, the context's bin-weight table read at
+ * every step, the inverses, first maximum, prior, the gate sum_p lag^2 > 4
+ * deciding whether the EMA updates, the float EMA with now_us = e * 1e6 / fs,
+ * and the grid solve on the EMA scores.
+ * The result is an ordinary tdoa_stream: it steps with tdoa_stream_step_f, is
+ * read with tdoa_stream_state_f (and tdoa_stream_state with est = NULL;
+ * stats[0] counts listed frames), and tdoa_stream_reset / tdoa_stream_destroy
+ * apply; graph mode and plain stream launches both work.  Kernel:
+ * k_stream_active, in place of a trigger.
+ * TDOA_ERR_INVALID, with tdoa_last_error naming the cause: a NULL argument; a
+ * DIRECT context (it reproduces the firmware, which has no such mode);
+ * activity_var outside [0, 2^30]; hop outside [1, N]; capture_len < N + 2 hop;
+ * an int16 ring that is not 2-byte aligned; a shape outside the GCC_PHAT LDS
+ * rule above.  The triggers' own 150 KiB LDS limit does not apply. */
+int tdoa_stream_create_continuous(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
+                                  const void *capture /* device [S][capture_len][M] */,
+                                  int64_t capture_len, int64_t activity_var, int use_graph,
+                                  tdoa_stream **out);
 /* One hop for every stream, asynchronous on `stream` (graph mode needs a
  * non-NULL stream; the captured graph is reused while `out` and `stream`
  * stay the same). */

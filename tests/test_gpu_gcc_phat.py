@@ -38,7 +38,9 @@ def _np(d):
     return {k: v.cpu().numpy() for k, v in d.items()}
 
 
-def check_phat(got, exp, grid=True):
+def check_phat(got, exp, grid=True, half_w=50, half_h=50, scale=24.0):
+    """half_w, half_h, scale: the context's grid (tests/test_gpu_grid_geometry.py); xy is the
+    closed form of the GPU's own cell, W = 2 half_w + 1."""
     s_exp = exp["scores_f"]
     assert np.abs(got["scores_f"] - s_exp).max() <= TOL_SCORE
     srt = np.sort(s_exp, axis=-1)
@@ -59,9 +61,9 @@ def check_phat(got, exp, grid=True):
         Lsel = Lg[np.arange(len(cells)), cells]
         assert (np.abs(Lsel[sure_c] - top[sure_c]) < 1e-9).all()
         assert np.abs(got["max_Lf"] - exp["max_Lf"])[lag_ok].max(initial=0) <= 1e-3
-        W = 101
-        xy = np.stack([(cells % W - 50).astype(np.float32) / np.float32(24.0),
-                       (50 - cells // W).astype(np.float32) / np.float32(24.0)], -1)
+        W = 2 * half_w + 1
+        xy = np.stack([(cells % W - half_w).astype(np.float32) / np.float32(scale),
+                       (half_h - cells // W).astype(np.float32) / np.float32(scale)], -1)
         assert (got["xy"] == xy).all()
     return sure.mean()
 

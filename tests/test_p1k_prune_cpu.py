@@ -87,7 +87,7 @@ def test_more_than_64_rows_have_no_table(dumped):
     assert T.shape[1] == 6510 and words.size == 0 and R.row_table(T, np.arange(6510)) is None
 
 
-def _peaked(rng, n, T):
+def _peaked(rng, n, T, K=K):
     """n frames of [3][K] scores: a bump of the lag prior's shape around a grid tuple, plus noise."""
     k = np.arange(K)
     c = T[:, rng.integers(0, T.shape[1], n)].T + rng.integers(-1, 2, (n, 3))
@@ -95,28 +95,33 @@ def _peaked(rng, n, T):
     return (amp * np.exp(-(k - c[..., None]) ** 2 / 36.0) + rng.normal(0, 4e-3, (n, 3, K))).astype(F32)
 
 
-def _cases(T, tab):
+def _cases(T, tab, K=K):
+    """kind -> [48][3][K] float32 scores for the table `tab` of the tuples T.  K: the lag
+    slots per pair (the module's 93 by default); the planted +-inf / NaN slots keep
+    their share of the range, 19..73 at K = 93.  A one-row table has no "planted_ties"."""
     rng = np.random.default_rng(0x9121)
     n = 48
+    lo, hi = K * 19 // 93, K * 74 // 93
     noise = lambda m=n: rng.normal(0, 5e-3, (m, 3, K)).astype(F32)  # noqa: E731
-    peaked = _peaked(rng, n, T)
+    peaked = _peaked(rng, n, T, K)
     const = np.full((n, 3, K), 0.25, F32)
     c = {"peaked": peaked, "flat_noise": noise(), "all_equal": const,
          "all_negative": (-rng.uniform(0.01, 1.0, (n, 3, K))).astype(F32),
          "all_negative_peaked": (peaked - F32(1.0)).astype(F32)}
     # exact ties: every score -1 but the slots of two tuples from different rows (0: sums are exact)
     ties = np.full((n, 3, K), -1.0, F32)
-    for f in range(n):
+    for f in range(n if tab["rows"] >= 2 else 0):
         ra, rb = rng.choice(tab["rows"], 2, replace=False)
         for r in (ra, rb):
             u = 64 * r + rng.integers(0, min(64, tab["U"] - 64 * r))
             ties[f, np.arange(3), tab["tuples"][:, u]] = 0.0
-    c["planted_ties"] = ties
+    if tab["rows"] >= 2:
+        c["planted_ties"] = ties
     inf = peaked.copy()
     for f in range(n):
-        inf[f, rng.integers(0, 3), rng.integers(19, 74, 3)] = np.inf if f % 3 else -np.inf
+        inf[f, rng.integers(0, 3), rng.integers(lo, hi, 3)] = np.inf if f % 3 else -np.inf
         if f % 4 == 0:
-            inf[f, rng.integers(0, 3), rng.integers(19, 74, 2)] = -np.inf
+            inf[f, rng.integers(0, 3), rng.integers(lo, hi, 2)] = -np.inf
     c["inf"] = inf
     nan = peaked.copy()
     for f in range(n):
@@ -124,7 +129,7 @@ def _cases(T, tab):
         if f % 4 == 3:
             nan[f, q] = np.nan  # every L is NaN: tuple 0, -inf
         else:
-            nan[f, q, rng.integers(19, 74, 1 + f % 6)] = np.nan
+            nan[f, q, rng.integers(lo, hi, 1 + f % 6)] = np.nan
     c["nan_one_pair"] = nan
     mixed = peaked.copy()
     mixed[1::4] = const[1::4]

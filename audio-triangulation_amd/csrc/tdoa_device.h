@@ -21,19 +21,6 @@
 
 namespace {
 
-// 16-B chunk k (8 int16 samples) of row `row` of a frame batch: int16 rows, or
-// the streaming batch's 8-bit rows (kp.frames_u8) widened from 8 bytes
-__device__ __forceinline__ uint4 frame_chunk(const tdoa_kparams &kp, const int16_t *frames, int64_t row, int k)
-{
-    if (kp.frames_u8) {
-        const uint2 b = reinterpret_cast<const uint2 *>(reinterpret_cast<const uint8_t *>(frames) +
-                                                        row * kp.N)[k];
-        return make_uint4(__builtin_amdgcn_perm(0u, b.x, 0x0C010C00u), __builtin_amdgcn_perm(0u, b.x, 0x0C030C02u),
-                          __builtin_amdgcn_perm(0u, b.y, 0x0C010C00u), __builtin_amdgcn_perm(0u, b.y, 0x0C030C02u));
-    }
-    return reinterpret_cast<const uint4 *>(frames + row * kp.N)[k];
-}
-
 // a streaming slot's frame in the capture ring (kp.frame_ring): its stream's
 // bytes (dma_sampler.c:17-23 round-robin), the absolute index of the frame's
 // first sample and that sample's ring index
@@ -52,7 +39,7 @@ __device__ __forceinline__ RingSlot ring_slot(const tdoa_kparams &kp, int64_t sl
 
 // chunk k (8 samples) of mic m of that frame: samples j + 8k + i (wrapping at
 // ring_len), zero before the stream's first sample -- the bytes the trigger
-// scanned (k_stream_trigger_p)
+// scanned
 __device__ __forceinline__ uint4 ring_chunk(const tdoa_kparams &kp, const RingSlot &rs, int m, int k)
 {
     const int M = kp.M;
@@ -282,8 +269,6 @@ __device__ void stage_frames(const tdoa_kparams &kp, const Smem &sm, const int16
             if (kp.frame_ring) {  // streaming batch: frame f0 + r / M from its stream's ring
                 const int fl = r / kp.M, m = r - fl * kp.M;
                 v = ring_chunk(kp, f0 + fl, m, k);
-            } else if (kp.frames_u8) {
-                v = frame_chunk(kp, frames, f0 * kp.M + r, k);
             } else {
                 v = src[c];
             }

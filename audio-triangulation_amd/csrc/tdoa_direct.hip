@@ -449,8 +449,6 @@ __device__ __forceinline__ void stage_mf(const tdoa_kparams &kp, const Smem &sm,
             if (kp.frame_ring) {  // streaming batch: frame f0 + r / M from its stream's ring
                 const int fl = r / kp.M, m = r - fl * kp.M;
                 v[i] = ring_chunk(kp, f0 + fl, m, k);
-            } else if (kp.frames_u8) {
-                v[i] = frame_chunk(kp, frames, f0 * kp.M + r, k);
             } else {
                 v[i] = reinterpret_cast<const uint4 *>(frames + f0 * kp.M * kp.N)[c];
             }

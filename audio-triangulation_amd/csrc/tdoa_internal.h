@@ -94,17 +94,17 @@ struct tdoa_stream_params {
     int32_t M, N, H, log2N, fs;
     int64_t capture_len;      // samples per stream in the capture ring
     const uint8_t *capture;   // [S][capture_len][M] 8-bit ADC bytes, round-robin; of a PCM16
-                              // pipeline int16 samples (k_stream_trigger16, k_stream_phat_pcm16 cast it)
+                              // pipeline int16 samples (its kernels cast it)
     int64_t *pos;             // [1] samples consumed (device clock)
     int64_t *ring_start;      // [S] sample index of the last trigger (rings restart there)
     int32_t *count;           // [1] frames triggered this step
     int32_t *count_next;      // [1] the next step's counter: zeroed by this step's trigger
                               // (two counters alternate by hop parity: no memset node)
+    // the hop's listed frames, written by its selector (a trigger or
+    // k_stream_active) and staged from the capture ring by the hop kernel
     int32_t *ids;             // [S] compact slot -> stream
-    int64_t *end;             // [S] samples consumed at the trigger
+    int64_t *end;             // [S] samples consumed at the frame's end (always >= N)
     int64_t *ring_at;         // [S] ring index of the slot's first frame sample
-                              // (persistent trigger: DIRECT reads the ring)
-    int16_t *frames;          // [S][M][N] triggered frames, compact (k_stream_trigger)
     int64_t *fresh;           // [S][P][K] their weighted scores (k_direct)
     int32_t *fresh_lags;      // [S][P]
     uint8_t *fresh_gate;      // [S]
@@ -178,32 +178,32 @@ int tdoa_launch_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const 
                       bool is_float, int64_t B, int num_peaks, int radius, float min_rel,
                       void *stream);
 size_t tdoa_stream_trigger_lds(int M, int N, int H);
-// *by_id: the launch wrote each triggered frame at its stream's index
-// (k_stream_trigger_p) instead of its compact slot -- the layout DIRECT reads
-int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *stream, bool *by_id);
-// the trigger on an int16 ring (k_stream_trigger16; sp.capture holds int16):
-// thr = trigger_var * (N/2)^2; firing streams are listed only (by_id form)
-int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_t thr, void *stream);
-// continuous mode's frame lister in place of a trigger (k_stream_active<T, M>,
-// T = int16_t for pcm16 else uint8_t): every stream whose frame [e - N, e),
-// e = pos + H >= N, has sum_m (N sum x_m^2 - (sum x_m)^2) >= thr, with
-// thr = activity_var * N^2; listed in the by_id form (ids, end, ring_at);
+// The hop's frame selectors.  Each lists the frames it chooses as sp.ids[slot],
+// sp.end[slot] (>= N: no frame reaches before its stream's start) and
+// sp.ring_at[slot], counts them in *sp.count and zeroes *sp.count_next; the hop
+// kernel (DIRECT or k_stream_phat*) stages each frame from its stream's ring.
+// The trigger: k_stream_trigger_p where it applies (8-bit rings, N = 2 hop,
+// M <= 4, aligned capture), else k_stream_trigger_lds<T> (T = int16_t for pcm16
+// else uint8_t); thr = trigger_var * (N/2)^2, POWER_THRESHOLD = 2 for 8-bit
+int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, int64_t thr, bool pcm16, void *stream);
+// continuous mode's frame lister in place of a trigger (k_stream_active<T, M>):
+// every stream whose frame [e - N, e), e = pos + H >= N, has
+// sum_m (N sum x_m^2 - (sum x_m)^2) >= thr, with thr = activity_var * N^2;
 // ring_start is not touched
 int tdoa_launch_stream_active(const tdoa_stream_params &sp, int64_t S, int64_t thr, bool pcm16, void *stream);
 int tdoa_launch_stream_update(const tdoa_stream_params &sp, const tdoa_kparams &kp,
                               const tdoa_stream_kout &out, int64_t S, void *stream);
-// the GCC_PHAT hop after the trigger (tdoa_stream_phat.hip, k_stream_phat):
+// the GCC_PHAT hop after the selector (tdoa_stream_phat.hip, k_stream_phat):
 // its dynamic LDS, whether the shape fits, the launch size for S streams
 // (resident workgroups, capped by `cap` > 0), and the launch -- est is the
-// float EMA state [S][P][K] (sp.est, sp.fresh* are not read), by_id as
-// tdoa_launch_stream_trigger answered; pcm16: the int16-ring kernel
-// (k_stream_phat_pcm16, after tdoa_launch_stream_trigger16; by_id is not read)
+// float EMA state [S][P][K] (sp.est, sp.fresh* are not read); pcm16: the
+// int16-ring kernel (k_stream_phat_pcm16)
 size_t tdoa_stream_phat_lds(const tdoa_kparams &kp);
 bool tdoa_stream_phat_fits(const tdoa_kparams &kp);
 int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16 = false);
 int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
-                            float *est, float *max_Lf, int64_t S, bool by_id, float phat_eps, int grid,
-                            void *stream, bool pcm16 = false);
+                            float *est, float *max_Lf, int64_t S, float phat_eps, int grid, void *stream,
+                            bool pcm16 = false);
 int tdoa_launch_average(const tdoa_kparams &kp, int64_t S, int64_t *est,
                         const int64_t *fresh, const float *decay, int32_t *best,
                         const tdoa_kout *solve, void *stream);

@@ -83,7 +83,7 @@ struct tdoa_kparams {
     const uint16_t *fg_tup;    // [U][32] the regrouped tuples as compact element indices (wc_off + lag - wc_lo)
     int32_t fg_ok;             // the tables exist (n <= 15, wc_CK <= 2048, bb_NT <= 256, P <= 32)
     // DIRECT on the streaming batch read straight from the capture ring (the
-    // persistent trigger lists the firing streams and copies nothing): frame f
+    // triggers list the firing streams and copy nothing): frame f
     // of the batch is stream frame_ids[f]'s samples from ring index
     // frame_ring_at[f] (absolute sample frame_end[f] - N; earlier than the
     // stream's first sample reads as 0); frame_ring null: frame f is frames[f]
@@ -92,14 +92,13 @@ struct tdoa_kparams {
     int64_t ring_len;
     const int64_t *frame_end;      // [B] samples consumed at the trigger
     const int64_t *frame_ring_at;  // [B] ring index of the frame's first sample
-    // the streaming batch's frames are 8-bit ADC samples ([.][M][N] bytes, the
-    // capture ring's values: half the bytes of int16 copies), widened to int16
-    // when staged
-    int32_t frames_u8;
+    // reserved, always 0 (once the flag of a compact 8-bit frame batch): the
+    // four bytes stay so that no other field moves
+    int32_t reserved0;
     // sample format of a GCC_PHAT batch (tdoa_set_sample_format): 0 the 8-bit
     // ADC front end, 1 full-range int16 (TDOA_SAMPLES_PCM16).  It picks the
     // launch's kernels on the host; no kernel reads it.  It fills the four
-    // bytes of padding ahead of mic_xy, so no other field moves and every
+    // bytes between reserved0 and mic_xy, so no other field moves and every
     // kernel's argument offsets stay as they were
     int32_t pcm16;
     // least-squares refinement (tdoa_ls.hip)

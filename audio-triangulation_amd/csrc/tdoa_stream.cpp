@@ -1,17 +1,20 @@
 // tdoa_stream.cpp -- host side of the streaming pipeline (include/tdoa.h,
 // kernels in tdoa_stream.hip): device state, the per-hop kernel sequence
-//   k_stream_trigger -> k_direct_mfma (device-sized batch, EMA + grid on the
-//   EMA scores fused) -- or, for shapes that kernel does not solve, k_direct ->
-//   k_stream_update -- and its hipGraph capture / replay.  The hop's trigger
-//   counter alternates between two slots by hop parity: the trigger zeroes the
-//   other slot for the next hop (a memset node cost 3.9 us per hop), so the
-//   two parities are two captured graphs.
-// A GCC_PHAT pipeline runs the same trigger, then k_stream_phat
-// (tdoa_stream_phat.hip): float scores, float EMA state, max_Lf.  On an int16
-// ring (tdoa_stream_create_pcm16) it runs k_stream_trigger16, then
-// k_stream_phat_pcm16.  A continuous pipeline (tdoa_stream_create_continuous)
-// runs k_stream_active in place of either trigger -- one candidate frame per
-// stream and hop behind an activity threshold -- then the same k_stream_phat*.
+//   selector -> hop kernel
+// and its hipGraph capture / replay.  The selector is the trigger
+// (k_stream_trigger_p, or k_stream_trigger_lds<T> for the other hop shapes and
+// int16 rings) or, in a continuous pipeline (tdoa_stream_create_continuous),
+// k_stream_active -- one candidate frame per stream and hop behind an activity
+// threshold.  Every selector lists the frames it chooses (stream, end, ring
+// index), none copies a frame; every hop kernel stages its frames from the
+// capture ring.  The hop kernel of a DIRECT pipeline is k_direct_mfma
+// (device-sized batch, EMA + grid on the EMA scores fused) -- or, for shapes
+// that kernel does not solve, k_direct -> k_stream_update; of a GCC_PHAT
+// pipeline k_stream_phat (tdoa_stream_phat.hip: float scores, float EMA state,
+// max_Lf), k_stream_phat_pcm16 on an int16 ring (tdoa_stream_create_pcm16).
+// The hop's frame counter alternates between two slots by hop parity: the
+// selector zeroes the other slot for the next hop (a memset node cost 3.9 us
+// per hop), so the two parities are two captured graphs.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -61,15 +64,15 @@ struct tdoa_stream {
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
     step_graph g[2];  // one per counter parity; released before mem
-    bool phat = false;      // GCC_PHAT pipeline: k_stream_phat after the trigger
+    bool phat = false;      // GCC_PHAT pipeline: k_stream_phat after the selector
     float *est_f = nullptr; // ... its EMA state [S][P][K] (sp.est is null)
     float phat_eps = 0.0f;
     int phat_grid = 1;      // k_stream_phat's launch size
-    bool pcm16 = false;     // int16 capture ring (tdoa_stream_create_pcm16): k_stream_trigger16,
+    bool pcm16 = false;     // int16 capture ring (tdoa_stream_create_pcm16): k_stream_trigger_lds<int16_t>,
                             // k_stream_phat_pcm16; the format is the pipeline's from creation on
-    int64_t trig_thr = 0;   // ... its trigger threshold, trigger_var * (N/2)^2
     bool continuous = false;  // tdoa_stream_create_continuous: k_stream_active lists the frames, no trigger
-    int64_t act_thr = 0;      // ... its threshold, activity_var * N^2
+    int64_t thr = 0;        // the selector's threshold: trigger_var * (N/2)^2 (POWER_THRESHOLD = 2,
+                            // sample_compute.h:21, for 8-bit rings), continuous: activity_var * N^2
 };
 
 namespace {
@@ -96,15 +99,8 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
     tdoa_stream_params sp = st->sp;
     sp.count = st->sp.count + par;
     sp.count_next = st->sp.count + (1 - par);
-    bool by_id = false;  // where DIRECT finds the frames: the capture ring or compact copies
-    int rc;
-    if (st->continuous) {
-        rc = tdoa_launch_stream_active(sp, st->S, st->act_thr, st->pcm16, s);
-        by_id = true;  // listed only: k_stream_phat stages each frame from its stream's ring
-    } else {
-        rc = st->pcm16 ? tdoa_launch_stream_trigger16(sp, st->S, st->trig_thr, s)
-                       : tdoa_launch_stream_trigger(sp, st->S, s, &by_id);
-    }
+    int rc = st->continuous ? tdoa_launch_stream_active(sp, st->S, st->thr, st->pcm16, s)
+                            : tdoa_launch_stream_trigger(sp, st->S, st->thr, st->pcm16, s);
     if (rc)
         return rc;
     if (st->phat) {
@@ -114,18 +110,16 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
         kp.bin_w = ck->bin_w;
         kp.bin_lo = ck->bin_lo;
         kp.bin_hi = ck->bin_hi;
-        return tdoa_launch_stream_phat(sp, kp, to_kout(out), st->est_f, out.max_Lf, st->S, by_id, st->phat_eps,
+        return tdoa_launch_stream_phat(sp, kp, to_kout(out), st->est_f, out.max_Lf, st->S, st->phat_eps,
                                        st->phat_grid, s, st->pcm16);
     }
+    // DIRECT stages each listed frame from its stream's ring: no frame pointer
     tdoa_kparams kp = st->kp;
-    if (by_id) {  // listed only: DIRECT stages each frame from its stream's ring
-        kp.frame_ids = sp.ids;
-        kp.frame_ring = sp.capture;
-        kp.ring_len = sp.capture_len;
-        kp.frame_end = sp.end;
-        kp.frame_ring_at = sp.ring_at;
-    }
-    kp.frames_u8 = 1;  // k_stream_trigger's compact copies are 8-bit
+    kp.frame_ids = sp.ids;
+    kp.frame_ring = sp.capture;
+    kp.ring_len = sp.capture_len;
+    kp.frame_end = sp.end;
+    kp.frame_ring_at = sp.ring_at;
     if (tdoa_direct_ema_fits(kp)) {
         // k_direct_mfma runs the EMA and the grid on the EMA scores itself:
         // results straight into the caller's slots, no fresh-score round trip
@@ -138,13 +132,13 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
         ko.cell = ef.so.cell;
         ko.xy = ef.so.xy;
         ko.max_L = ef.so.max_L;
-        return tdoa_launch_direct(kp, ko, sp.frames, st->S, false, s, nullptr, sp.count, &ef);
+        return tdoa_launch_direct(kp, ko, nullptr, st->S, false, s, nullptr, sp.count, &ef);
     }
     tdoa_kout ko{};
     ko.lags = sp.fresh_lags;
     ko.gate = sp.fresh_gate;
     ko.weighted = sp.fresh;
-    rc = tdoa_launch_direct(kp, ko, sp.frames, st->S, false, s, nullptr, sp.count);
+    rc = tdoa_launch_direct(kp, ko, nullptr, st->S, false, s, nullptr, sp.count);
     if (rc)
         return rc;
     return tdoa_launch_stream_update(sp, st->kp, to_kout(out), st->S, s);
@@ -216,9 +210,9 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->use_graph = use_graph;
     st->phat = phat;
     st->pcm16 = pcm16;
-    st->trig_thr = pcm16 && !continuous ? trigger_var * (int64_t)(N / 2) * (N / 2) : 0;  // <= 2^30 * 2^22
     st->continuous = continuous;
-    st->act_thr = continuous ? var * (int64_t)N * N : 0;  // <= 2^30 * 2^24
+    // <= 2^30 * 2^24; an 8-bit trigger's variance is the firmware's POWER_THRESHOLD (sample_compute.h:21)
+    st->thr = continuous ? var * (int64_t)N * N : (pcm16 ? trigger_var : 2) * (int64_t)(N / 2) * (N / 2);
     if (phat) {
         st->phat_eps = tdoa_ctx_phat_eps(ctx);
         // TDOA_STREAM_PHAT_GRID=n caps k_stream_phat's launch size (A/B runs)
@@ -235,7 +229,7 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     };
     // (a GCC_PHAT pipeline keeps the frame's scores on chip: no fresh* buffers, float EMA state)
     const size_t o_pos = take(8), o_count = take(8), o_rs = take(S * 8), o_ids = take(S * 4),
-                 o_end = take(S * 8), o_at = take(S * 8), o_frames = take(pcm16 || continuous ? 0 : S * M * N),
+                 o_end = take(S * 8), o_at = take(S * 8),
                  o_fresh = take(phat ? 0 : S * P * K * 8), o_fl = take(phat ? 0 : S * P * 4),
                  o_fg = take(phat ? 0 : S), o_est = take(S * P * K * (phat ? 4 : 8)), o_last = take(S * 8),
                  o_stats = take(16);
@@ -256,7 +250,6 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     sp.ids = (int32_t *)(b + o_ids);
     sp.end = (int64_t *)(b + o_end);
     sp.ring_at = (int64_t *)(b + o_at);
-    sp.frames = pcm16 || continuous ? nullptr : (int16_t *)(b + o_frames);  // the compact-copy trigger's only
     sp.fresh = phat ? nullptr : (int64_t *)(b + o_fresh);
     sp.fresh_lags = phat ? nullptr : (int32_t *)(b + o_fl);
     sp.fresh_gate = phat ? nullptr : (uint8_t *)(b + o_fg);

@@ -2,29 +2,33 @@
 // independent mic-array streams, one hop of H samples per step (BASELINE
 // config 5).  Three kernels per step (plus k_direct on the triggered frames):
 //
-//   k_stream_trigger  one workgroup per stream: reads the hop's 8-bit ADC
-//                     bytes (dma_sampler.c:17-23, round-robin per mic, read
-//                     as sample_t at sample_compute.h:67-73) and the N-1
-//                     samples before it from the capture ring, evaluates the
-//                     trigger of sample_compute.h:75-91 after every sample of
-//                     the hop -- half powers of rolling_buffer.c:73-85 from
+//   k_stream_trigger_lds<T>
+//                     one workgroup per stream: reads the hop's samples (8-bit
+//                     ADC bytes, dma_sampler.c:17-23, round-robin per mic, read
+//                     as sample_t at sample_compute.h:67-73; or int16) and the
+//                     N-1 samples before it from the capture ring, evaluates
+//                     the trigger of sample_compute.h:75-91 after every sample
+//                     of the hop -- half powers of rolling_buffer.c:73-85 from
 //                     LDS prefix sums -- and takes the first firing sample
 //                     at least N samples after the stream's last trigger
 //                     (the rings restart empty after a trigger,
-//                     sample_compute.h:55-57).  A firing stream appends its
-//                     frame (the ring oldest..newest) to a compact batch.
-//   k_direct          (tdoa_direct.hip) on the compact batch, its size read
-//                     from device memory: write_out, normalize, window,
-//                     xcorr, prior, gate.
+//                     sample_compute.h:55-57).  A firing stream is listed:
+//                     ids[slot], end[slot], ring_at[slot].
+//   k_stream_trigger_p  the same trigger in registers, one wave per stream
+//                     (8-bit rings, N = 2 hop, M <= 4, aligned capture).
+//   k_direct          (tdoa_direct.hip) on the listed frames, their number read
+//                     from device memory, each staged from its stream's ring:
+//                     write_out, normalize, window, xcorr, prior, gate.
 //   k_stream_update   one workgroup per compact slot: for gated frames the
 //                     EMA of correlations.c:38-63 on the stream's state
 //                     (clock now_us = end * 1e6 / fs) and the grid solve on
 //                     the EMA scores (vga_heatmap.h:99-108 runs on corr_*);
 //                     advances the device sample clock by H.
-// A GCC_PHAT pipeline runs k_stream_phat (tdoa_stream_phat.hip) after the
-// trigger -- k_stream_trigger16 on an int16 ring -- or, in continuous mode,
-// after k_stream_active, which lists one candidate frame per stream and hop
-// behind an activity threshold instead of triggering.
+// A GCC_PHAT pipeline runs k_stream_phat* (tdoa_stream_phat.hip) after the
+// trigger or, in continuous mode, after k_stream_active, which lists one
+// candidate frame per stream and hop behind an activity threshold instead of
+// triggering.  Every selector lists, every hop kernel reads the ring: no
+// kernel writes a copy of a frame.
 //
 // Built with -ffp-contract=off: the EMA's float steps round as the
 // reference's IEEE host build does.
@@ -43,7 +47,7 @@ namespace {
 
 constexpr int TPB = 256;
 constexpr int MAX_CAND = 16;  // hop <= 4096 candidates, TPB per pass
-constexpr int TRIG16_LB = 16; // k_stream_trigger16: ring loads in flight per thread
+constexpr int TRIG_LB = 16;   // k_stream_trigger_lds: ring loads in flight per thread
 
 // inclusive block scan of per-thread totals (int32 and int64 together)
 __device__ __forceinline__ void block_exclusive_scan(int &v1, long long &v2, int *s1,
@@ -77,143 +81,23 @@ __device__ __forceinline__ void block_exclusive_scan(int &v1, long long &v2, int
     __syncthreads();
 }
 
-__global__ void __launch_bounds__(TPB) k_stream_trigger(tdoa_stream_params sp)
-{
-    if (blockIdx.x == 0 && threadIdx.x == 0 && sp.count_next)
-        *sp.count_next = 0;  // the next hop's counter (last read by the previous hop)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int M = sp.M, N = sp.N, H = sp.H, L = N + H - 1, tid = threadIdx.x;
-    int16_t *xs = (int16_t *)smem;                                   // [M][L]
-    size_t o = (((size_t)M * L * 2) + 15) & ~(size_t)15;
-    int *Q1 = (int *)(smem + o);                                      // [L + 1]
-    o += (((size_t)(L + 1) * 4) + 15) & ~(size_t)15;
-    long long *Q2 = (long long *)(smem + o);                          // [L + 1]
-    __shared__ int sc1[TPB / 64];
-    __shared__ long long sc2[TPB / 64];
-    __shared__ int first, slot;
-
-    const int64_t s = blockIdx.x;
-    const int64_t pos = *sp.pos;           // samples consumed before this hop
-    const int64_t base = pos + 1 - N;      // stream index of local sample 0
-    const uint8_t *cap = sp.capture + (size_t)s * sp.capture_len * M;
-    // local samples l = 0..L-1 <-> stream index base + l (zero before the stream starts)
-    {
-        int64_t j0 = base % sp.capture_len;
-        if (j0 < 0)
-            j0 += sp.capture_len;
-        for (int i = tid; i < L * M; i += TPB) {
-            const int l = i / M, m = i - l * M;
-            int64_t j = j0 + l;
-            if (j >= sp.capture_len)
-                j -= sp.capture_len;
-            xs[m * L + l] = base + l < 0 ? (int16_t)0 : (int16_t)cap[(size_t)j * M + m];
-        }
-    }
-    if (tid == 0)
-        first = INT_MAX;
-    __syncthreads();
-
-    // per candidate a (frame = local [a, a + N), end = pos + 1 + a): sum over
-    // mics of the outgoing (older half) and incoming (newer half) powers
-    const int hb = sp.log2N - 1;
-    long long pout[MAX_CAND], pin[MAX_CAND];
-#pragma unroll
-    for (int c = 0; c < MAX_CAND; c++)
-        pout[c] = pin[c] = 0;
-    const int per = (L + 1 + TPB - 1) / TPB;  // prefix entries per thread
-    for (int m = 0; m < M; m++) {
-        const int16_t *x = xs + m * L;
-        // Q[l] = sum_{l' < l} x, Q2 the same of x^2 (rolling_buffer.c:22-32 totals)
-        int t1 = 0;
-        long long t2 = 0;
-        const int l0 = tid * per;
-        for (int k = 0; k < per; k++) {
-            const int l = l0 + k;
-            if (l < L) {
-                const int v = x[l];
-                t1 += v;
-                t2 += (long long)v * v;
-            }
-        }
-        int e1 = t1;
-        long long e2 = t2;
-        block_exclusive_scan(e1, e2, sc1, sc2);
-        for (int k = 0; k <= per; k++) {
-            const int l = l0 + k;
-            if (l <= L && (k < per || l == L)) {
-                Q1[l] = e1;
-                Q2[l] = e2;
-            }
-            if (k < per && l < L) {
-                const int v = x[l];
-                e1 += v;
-                e2 += (long long)v * v;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < MAX_CAND; c++) {
-            const int a = tid + TPB * c;
-            if (a < H) {
-                const int h = N >> 1;
-                const long long so1 = Q1[a + h] - Q1[a], so2 = Q2[a + h] - Q2[a];
-                const long long si1 = Q1[a + N] - Q1[a + h], si2 = Q2[a + N] - Q2[a + h];
-                pout[c] += (long long)((unsigned long long)so2 << hb) - so1 * so1;
-                pin[c] += (long long)((unsigned long long)si2 << hb) - si1 * si1;
-            }
-        }
-        __syncthreads();
-    }
-    const long long thr = (long long)2 << (2 * hb);  // POWER_THRESHOLD, sample_compute.h:21
-    const int64_t rs = sp.ring_start[s];
-    // full ring: at least N samples since the last trigger
-    const int64_t amin = rs + N - pos - 1;
-#pragma unroll
-    for (int c = 0; c < MAX_CAND; c++) {
-        const int a = tid + TPB * c;
-        if (a < H && a >= amin && pout[c] > thr + pin[c]) {
-            atomicMin(&first, a);
-            break;  // candidates grow with c: this thread's first is its best
-        }
-    }
-    __syncthreads();
-    const int a = first;
-    if (a == INT_MAX)
-        return;
-    if (tid == 0) {
-        slot = atomicAdd(sp.count, 1);
-        const int64_t end = pos + 1 + a;
-        if (slot < (int)gridDim.x) {  // one slot per stream (see k_stream_trigger_p)
-            sp.ids[slot] = (int32_t)s;
-            sp.end[slot] = end;
-        }
-        sp.ring_start[s] = end;
-    }
-    __syncthreads();
-    if (slot >= (int)gridDim.x)
-        return;
-    // the frame as 8-bit samples (the capture's values; DIRECT widens them,
-    // kp.frames_u8), four per dword store
-    uint32_t *dst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(sp.frames) + (size_t)slot * M * N);
-    for (int i = tid; i < M * N / 4; i += TPB) {
-        const int m = (4 * i) / N, n = 4 * i - m * N;
-        const int16_t *x = xs + m * L + a + n;
-        dst[i] = (uint32_t)(uint8_t)x[0] | (uint32_t)(uint8_t)x[1] << 8 | (uint32_t)(uint8_t)x[2] << 16 |
-                 (uint32_t)(uint8_t)x[3] << 24;
-    }
-}
-
-// ------------------------------------------------- the trigger on int16 rings
-// tdoa_stream_create_pcm16 (include/tdoa.h): k_stream_trigger's rule on int16
-// samples with the caller's threshold, thr = trigger_var * (N/2)^2.  sp.capture
-// points at int16 [S][capture_len][M] (2-byte loads: a stream's ring starts at
-// s * capture_len * M * 2 bytes, 4-byte aligned only when capture_len * M is
-// even).  One workgroup per stream, the same LDS prefix sums; per candidate one
-// int64 accumulator, sum_m pw(m, O) - pw(m, I): |pw| <= h^2 2^30 = 2^52 at
-// h = 2048, 2^55 over 8 mics, the prefix sums of x below (N + H) 2^15 <= 2^28
-// and those of x^2 below 2^43.  A firing stream is listed (ids, end, ring_at):
-// k_stream_phat<PCM16> stages the frame from the ring, no copy is written.
-__global__ void __launch_bounds__(TPB) k_stream_trigger16(tdoa_stream_params sp, long long thr)
+// ------------------------------------------------- the LDS trigger, any hop shape
+// The trigger of sample_compute.h:75-91 on a ring of T = uint8_t (ADC bytes) or
+// int16_t (tdoa_stream_create_pcm16, include/tdoa.h) samples: sp.capture points
+// at T [S][capture_len][M], read element by element (a stream's ring starts at
+// s * capture_len * M elements: an int16 ring is 4-byte aligned only when
+// capture_len * M is even).  thr is the host's: POWER_THRESHOLD (N/2)^2 =
+// 2 (N/2)^2 (sample_compute.h:21) for 8-bit, trigger_var (N/2)^2 for int16.
+// One workgroup per stream, LDS prefix sums; per candidate one int64
+// accumulator, sum_m pw(m, O) - pw(m, I) > thr -- the reference's pout > thr +
+// pin exactly, nothing overflows: int16 |pw| <= h^2 2^30 = 2^52 at h = 2048,
+// 2^55 over 8 mics, the prefix sums of x below (N + H) 2^15 <= 2^28 and those
+// of x^2 below 2^43; uint8 |pw| <= h^2 2^16 = 2^38, 2^41 over 8 mics, the
+// prefix sums below 2^21 and 2^29.  A firing stream is listed (ids, end,
+// ring_at): DIRECT and k_stream_phat* stage the frame from the ring, no copy
+// is written.
+template <typename T>
+__global__ void __launch_bounds__(TPB) k_stream_trigger_lds(tdoa_stream_params sp, long long thr)
 {
     if (blockIdx.x == 0 && threadIdx.x == 0 && sp.count_next)
         *sp.count_next = 0;  // the next hop's counter (last read by the previous hop)
@@ -237,13 +121,13 @@ __global__ void __launch_bounds__(TPB) k_stream_trigger16(tdoa_stream_params sp,
         return;  // fired during the previous hop: no candidate of this one is eligible
     const int64_t base = pos + 1 - N;      // stream index of local sample 0
     const int64_t cl = sp.capture_len;
-    const int16_t *cap = reinterpret_cast<const int16_t *>(sp.capture) + (size_t)s * cl * M;
+    const T *cap = reinterpret_cast<const T *>(sp.capture) + (size_t)s * cl * M;
     int64_t j0 = base % cl;
     if (j0 < 0)
         j0 += cl;
     // local samples l = 0..L-1 <-> stream index base + l (zero before the stream
     // starts): ring elements e0 + i (i = l M + m), contiguous modulo the ring's
-    // cl M, de-interleaved into xs.  TRIG16_LB loads are in flight per thread
+    // cl M, de-interleaved into xs.  TRIG_LB loads are in flight per thread
     // before the first is used (one load per trip waited out its latency 18
     // times at config 5), and a thread's (l, m) advance by TPB elements per
     // load without a division.
@@ -254,18 +138,18 @@ __global__ void __launch_bounds__(TPB) k_stream_trigger16(tdoa_stream_params sp,
         const int nz = base < 0 ? (base < -(int64_t)L ? L : (int)-base) : 0;  // samples before the stream's start
         const int dl = TPB / M, dm = TPB - dl * M;
         int l = tid / M, m = tid - l * M;
-        for (int i0 = tid; i0 < tot; i0 += TRIG16_LB * TPB) {
-            int16_t v[TRIG16_LB];
+        for (int i0 = tid; i0 < tot; i0 += TRIG_LB * TPB) {
+            T v[TRIG_LB];
 #pragma unroll
-            for (int k = 0; k < TRIG16_LB; k++) {
+            for (int k = 0; k < TRIG_LB; k++) {
                 const int i = i0 + k * TPB;
                 const int64_t e = (i < iw ? e0 : e0 - ring) + i;  // in [0, ring)
-                v[k] = i < tot ? cap[e] : (int16_t)0;
+                v[k] = i < tot ? cap[e] : (T)0;
             }
 #pragma unroll
-            for (int k = 0; k < TRIG16_LB; k++) {
+            for (int k = 0; k < TRIG_LB; k++) {
                 if (i0 + k * TPB < tot)
-                    xs[m * L + l] = l < nz ? (int16_t)0 : v[k];
+                    xs[m * L + l] = l < nz ? (int16_t)0 : (int16_t)v[k];
                 l += dl;
                 m += dm;
                 if (m >= M) {
@@ -358,7 +242,7 @@ __global__ void __launch_bounds__(TPB) k_stream_trigger16(tdoa_stream_params sp,
 // mic: candidate a = Gk + i needs the prefix sums at a, a + N/2 = a + H and
 // a + N = a + 2H, i.e. at position i of the lane's own three chunks.  The chunk
 // totals are wave-scanned (DPP), the rest is a running sum in registers.  Same
-// trigger as k_stream_trigger (sample_compute.h:75-91, rolling_buffer.c:73-85).
+// trigger as k_stream_trigger_lds (sample_compute.h:75-91, rolling_buffer.c:73-85).
 
 // inclusive wave scan (rows by row_shr, then row_bcast:15 / :31)
 __device__ __forceinline__ int wave_scan_incl(int v)
@@ -1044,8 +928,8 @@ size_t tdoa_stream_trigger_lds(int M, int N, int H)
     return ((M * L * 2 + 15) & ~(size_t)15) + (((L + 1) * 4 + 15) & ~(size_t)15) + (L + 1) * 8;
 }
 
-// the persistent register scan applies (N = 2H, config 5: N 1024, hop 512;
-// aligned capture); it writes each frame at its stream's index
+// the persistent register scan applies (8-bit rings; N = 2H, config 5: N 1024,
+// hop 512; aligned capture)
 static bool trigger_p_applies(const tdoa_stream_params &sp)
 {
     return sp.N == 2 * sp.H && ((uintptr_t)sp.capture & 3) == 0 &&
@@ -1080,41 +964,30 @@ static void launch_trigger_m(const tdoa_stream_params &sp, int64_t S, hipStream_
         launch_trigger_p<G, 4>(sp, S, st);
 }
 
-int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, void *stream, bool *by_id)
+int tdoa_launch_stream_trigger(const tdoa_stream_params &sp, int64_t S, int64_t thr, bool pcm16, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
-    if (trigger_p_applies(sp)) {
+    if (!pcm16 && trigger_p_applies(sp)) {
         if (sp.H == 256)
             launch_trigger_m<4>(sp, S, st);
         else if (sp.H == 512)
             launch_trigger_m<8>(sp, S, st);
         else
             launch_trigger_m<16>(sp, S, st);
-        *by_id = true;  // firing streams listed only: DIRECT reads their frames from the ring
         hipError_t e = hipGetLastError();
         return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger_p launch");
     }
-    *by_id = false;  // frames in compact slots
     if (sp.H > TPB * MAX_CAND)
         return tdoa_set_error(-1, "stream: hop too large");
-    const size_t lds = tdoa_stream_trigger_lds(sp.M, sp.N, sp.H);
+    const size_t lds = tdoa_stream_trigger_lds(sp.M, sp.N, sp.H);  // xs is int16 for both ring types
     if (lds > 150 * 1024)
         return tdoa_set_error(-1, "stream: (frame_len + hop) x mics exceeds the LDS budget");
-    hipLaunchKernelGGL(k_stream_trigger, dim3((unsigned)S), dim3(TPB), lds, st, sp);
+    if (pcm16)
+        hipLaunchKernelGGL(k_stream_trigger_lds<int16_t>, dim3((unsigned)S), dim3(TPB), lds, st, sp, (long long)thr);
+    else
+        hipLaunchKernelGGL(k_stream_trigger_lds<uint8_t>, dim3((unsigned)S), dim3(TPB), lds, st, sp, (long long)thr);
     hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger launch");
-}
-
-int tdoa_launch_stream_trigger16(const tdoa_stream_params &sp, int64_t S, int64_t thr, void *stream)
-{
-    if (sp.H > TPB * MAX_CAND)
-        return tdoa_set_error(-1, "stream: hop too large");
-    const size_t lds = tdoa_stream_trigger_lds(sp.M, sp.N, sp.H);  // xs is int16 in both triggers
-    if (lds > 150 * 1024)
-        return tdoa_set_error(-1, "stream: (frame_len + hop) x mics exceeds the LDS budget");
-    hipLaunchKernelGGL(k_stream_trigger16, dim3((unsigned)S), dim3(TPB), lds, (hipStream_t)stream, sp, (long long)thr);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger16 launch");
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_trigger_lds launch");
 }
 
 template <typename T, int M>

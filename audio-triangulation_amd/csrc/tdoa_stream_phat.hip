@@ -4,10 +4,10 @@
 //
 //   k_stream_phat  one 256-thread workgroup per triggered slot, persistent over
 //                  the device-side count.  Per slot: the frame's 8-bit samples
-//                  from the capture ring (k_stream_trigger_p lists the firing
-//                  streams only) or from the trigger's compact copy -- or, as
-//                  k_stream_phat_pcm16, its int16 samples from an int16 ring
-//                  and the 16-bit front end (TDOA_SAMPLES_PCM16); per mic
+//                  from its stream's capture ring (the selectors list frames,
+//                  none copies one) -- or, as k_stream_phat_pcm16, its int16
+//                  samples from an int16 ring and the 16-bit front end
+//                  (TDOA_SAMPLES_PCM16); per mic
 //                  the integer front end, the complex FFT_N of z[n] = x[2n] +
 //                  i x[2n+1] in LDS, the real-FFT split and the PHAT unit
 //                  spectrum U_m = X_m / sqrt(|X_m|^2 + eps), kept in LDS for
@@ -77,7 +77,7 @@ __device__ __forceinline__ float ema_step(float est, float fresh, float dec)
 
 __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa_kparams kp, tdoa_stream_kout out,
                                                      float *__restrict__ est_all, float *__restrict__ max_Lf,
-                                                     int nstreams, int by_id, float e2)
+                                                     int nstreams, float e2)
 {
     constexpr bool PCM16 = false;
 #include "tdoa_stream_phat_hop.inc"
@@ -89,7 +89,6 @@ __global__ void __launch_bounds__(TPB) k_stream_phat_pcm16(tdoa_stream_params sp
                                                            float *__restrict__ max_Lf, int nstreams, float e2)
 {
     constexpr bool PCM16 = true;
-    constexpr int by_id = 1;
 #include "tdoa_stream_phat_hop.inc"
 }
 
@@ -133,8 +132,8 @@ int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16
 }
 
 int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
-                            float *est, float *max_Lf, int64_t S, bool by_id, float phat_eps, int grid,
-                            void *stream, bool pcm16)
+                            float *est, float *max_Lf, int64_t S, float phat_eps, int grid, void *stream,
+                            bool pcm16)
 {
     if (!tdoa_stream_phat_fits(kp))
         return tdoa_set_error(-1, "stream GCC_PHAT: shape exceeds the LDS budget");
@@ -147,8 +146,7 @@ int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp
         return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_phat_pcm16 launch");
     }
     hipLaunchKernelGGL(k_stream_phat, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TPB), tdoa_stream_phat_lds(kp),
-                       (hipStream_t)stream, sp, kp, out, est, max_Lf, (int)S, by_id ? 1 : 0,
-                       tdoa_phat_floor_int16(phat_eps));
+                       (hipStream_t)stream, sp, kp, out, est, max_Lf, (int)S, tdoa_phat_floor_int16(phat_eps));
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_phat launch");
 }

@@ -1,10 +1,10 @@
 // tdoa_stream_phat_hop.inc -- the body of k_stream_phat (8-bit capture rings) and
 // k_stream_phat_pcm16 (int16 rings, tdoa_stream_create_pcm16), as text: it
-// reads the kernel's parameters (sp, kp, out, est_all, max_Lf, nstreams, e2),
-// by_id and the constant PCM16 of the including scope.  PCM16: sp.capture
-// points at int16 samples, the slot's frame is staged from the ring
-// (k_stream_trigger16 lists firing streams only; by_id is not read) and the
-// front end is phat_front_end<true>; everything after it is the same text.
+// reads the kernel's parameters (sp, kp, out, est_all, max_Lf, nstreams, e2)
+// and the constant PCM16 of the including scope.  Either stages the slot's
+// frame from its stream's ring (every selector lists frames, none copies one).
+// PCM16: sp.capture points at int16 samples and the front end is
+// phat_front_end<true>; everything after it is the same text.
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int N = kp.N, M = kp.M, P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6, nwaves = TPB / 64;
@@ -56,9 +56,10 @@
                 const uint32_t lo = (uint16_t)cap[(size_t)j0 * M + m], hi = (uint16_t)cap[(size_t)j1 * M + m];
                 reinterpret_cast<uint32_t *>(U + (size_t)m * N)[q] = lo | hi << 16;
             }
-        } else if (by_id) {
+        } else {
             // ring bytes [at * M, at * M + N * M) of the stream, wrapping at the
-            // ring's end; byte loads: a ring need not start 4-byte aligned
+            // ring's end; byte loads: a ring need not start 4-byte aligned.  No
+            // zero fill before the stream's start: every selector lists end >= N
             const uint8_t *cap = sp.capture + (size_t)s * ring_bytes;
             const int64_t b0 = sp.ring_at[slot] * M;
             for (int i = tid; i < N * M; i += TPB) {
@@ -67,16 +68,6 @@
                 if (b >= ring_bytes)
                     b -= ring_bytes;
                 reinterpret_cast<int16_t *>(U + (size_t)m * N)[l] = (int16_t)cap[b];
-            }
-        } else {
-            const uint32_t *src =
-                reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(sp.frames) + (size_t)slot * M * N);
-            for (int i = tid; i < M * N / 4; i += TPB) {
-                const int m = (4 * i) / N, n = 4 * i - m * N;
-                const uint32_t w = src[i];
-                uint32_t *dst = reinterpret_cast<uint32_t *>(U + (size_t)m * N) + (n >> 1);
-                dst[0] = (w & 0xFFu) | ((w >> 8) & 0xFFu) << 16;
-                dst[1] = ((w >> 16) & 0xFFu) | (w >> 24) << 16;
             }
         }
         __syncthreads();

@@ -142,3 +142,45 @@ def test_stream_register_trigger_shapes(oracle, N, hop, M):
     exp = oracle.stream_run(adc, N, 48000, loc.dims.S, loc.window(), lut)
     compare(recs, est, last, exp, loc.dims.P)
     loc.close()
+
+
+# (N, hop, M) -> (seed, hops): chosen on the CPU with the oracle alone; the
+# reference then has 40 / 55 triggers over the six streams, all of them gated
+LDS_RING_SHAPES = {(512, 192, 4): (600, 48),   # hop != N / 2
+                   (512, 256, 8): (600, 48)}   # M > 4 with N = 2 hop
+LDS_RING_MICS = {4: synth.square_mics(0.15), 8: synth.circle_mics()}  # test_gpu_stream_phat._loc's layouts
+
+
+@pytest.fixture(scope="module")
+def lds_ring_cases(oracle):
+    """shape -> (localizer, adc, reference), built once and shared by the resident and the ring run."""
+    made = {}
+
+    def get(shape):
+        if shape not in made:
+            N, hop, M = shape
+            seed, hops = LDS_RING_SHAPES[shape]
+            loc = Localizer(sample_rate_hz=48000, frame_len=N, num_mics=M, mic_xy=LDS_RING_MICS[M])
+            lut = loc.lut()
+            adc = synth.adc_stream(6, hop * hops, M, lut, loc.dims.S, seed).numpy()
+            exp = oracle.stream_run(adc, N, 48000, loc.dims.S, loc.window(), lut)
+            made[shape] = (loc, adc, exp)
+        return made[shape]
+
+    yield get
+    for loc, _, _ in made.values():
+        loc.close()
+
+
+@pytest.mark.parametrize("ring", [False, True], ids=["resident", "ring"])
+@pytest.mark.parametrize("N,hop,M", list(LDS_RING_SHAPES))
+def test_stream_lds_trigger_feeds_ring_stager(lds_ring_cases, N, hop, M, ring):
+    """The LDS trigger (k_stream_trigger_lds<uint8_t>: hop != N / 2, or more than
+    four mics) listing frames for DIRECT's ring stager with M != 3, ring_chunk's
+    byte path.  Once with the whole capture resident, once as a producer-fed ring
+    of N + 2 hop + 1 samples -- the smallest legal length plus one, odd: frames
+    wrap, at a different ring index every time round."""
+    loc, adc, exp = lds_ring_cases((N, hop, M))
+    assert exp["n_trig"].sum() >= 20 and exp["gate"].sum() >= 10
+    recs, est, last = run_pipeline(loc, adc, hop, capture_len=N + 2 * hop + 1 if ring else None)
+    compare(recs, est, last, exp, loc.dims.P)

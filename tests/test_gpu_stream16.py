@@ -1,5 +1,5 @@
 """Streaming GCC_PHAT on int16 capture rings (tdoa_stream_create_pcm16:
-k_stream_trigger16, k_stream_phat_pcm16) against the float64 reference of
+k_stream_trigger_lds<int16_t>, k_stream_phat_pcm16) against the float64 reference of
 tests/stream16_ref.py.
 
 Comparison rules: those of tests/test_gpu_stream_phat.py (its feed, compare

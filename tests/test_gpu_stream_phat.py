@@ -200,9 +200,9 @@ def test_band_limited_and_table_read_per_step(oracle, use_graph):
 # (N, hop, M, hops, seed, share of gated records whose cell may be skipped)
 SHAPES = [(2048, 1024, 4, 24, 2122, 0.25),  # the TW = 2 / P = 6 solve; the reference alone skips 16.9 %
           (512, 256, 2, 24, 584, 0.0),
-          (1024, 384, 3, 24, 424, 0.0),      # hop != N / 2: the compact-copy trigger path
+          (1024, 384, 3, 24, 424, 0.0),      # hop != N / 2: the LDS trigger (k_stream_trigger_lds)
           (256, 256, 3, 40, 77, 0.0),
-          (1024, 512, 8, 24, 808, 0.25)]     # the largest LDS shape; 8 mics take the compact-copy path too
+          (1024, 512, 8, 24, 808, 0.25)]     # the largest LDS shape; 8 mics take the LDS trigger too
 
 
 @pytest.mark.parametrize("N,hop,M,hops,seed,max_skip", SHAPES)

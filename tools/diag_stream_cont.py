@@ -6,7 +6,7 @@ continuous mode, on an 8-bit capture ring and on the int16 ring holding
 pipelines in one process, interleaved in three rounds.
 
 Pipelines ("mode/format"):
-    trig/adc8   trig/pcm16     the click trigger (k_stream_trigger_p, k_stream_trigger16)
+    trig/adc8   trig/pcm16     the click trigger (k_stream_trigger_p, k_stream_trigger_lds<int16_t>)
     cont0/*                    continuous, activity_var = 0: every stream, every hop
     contT/*                    continuous at the threshold that lists about the share
                                of streams the trigger lists (the matching quantile of

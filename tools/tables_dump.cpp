@@ -173,11 +173,11 @@ int main(int argc, char **argv)
     printf("\"kp\": {\"M\": %d, \"N\": %d, \"log2N\": %d, \"P\": %d, \"K\": %d, \"S\": %d, \"G\": %d, \"U\": %d, "
            "\"grid_W\": %d, \"half_w\": %d, \"half_h\": %d, \"grid_scale\": \"%08" PRIx32 "\", \"sbase\": %d, "
            "\"T\": %d, \"NSEG\": %d, \"PADW\": %d, \"RS\": %d, \"F\": %d, \"TW\": %d, \"xc3\": %d, \"bb_NT\": %d, "
-           "\"bb_wide\": %d, \"frames_u8\": %d, \"fs\": \"%08" PRIx32 "\", \"c\": \"%08" PRIx32
+           "\"bb_wide\": %d, \"fs\": \"%08" PRIx32 "\", \"c\": \"%08" PRIx32
            "\", \"height\": \"%08" PRIx32 "\", \"bin_lo\": %d, \"bin_hi\": %d}}\n",
            kp.M, kp.N, kp.log2N, kp.P, kp.K, kp.S, kp.G, kp.U, kp.grid_W, kp.half_w, kp.half_h,
            float_bits(kp.grid_scale), kp.sbase, kp.T, kp.NSEG, kp.PADW, kp.RS, kp.F, kp.TW, kp.xc3, kp.bb_NT,
-           kp.bb_wide, kp.frames_u8, float_bits(kp.fs), float_bits(kp.c), float_bits(kp.height), kp.bin_lo,
+           kp.bb_wide, float_bits(kp.fs), float_bits(kp.c), float_bits(kp.height), kp.bin_lo,
            kp.bin_hi);
     return 0;
 }

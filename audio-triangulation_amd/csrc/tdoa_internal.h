@@ -177,6 +177,17 @@ bool tdoa_peaks_fits(const tdoa_kparams &kp, bool is_float);
 int tdoa_launch_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const void *scores,
                       bool is_float, int64_t B, int num_peaks, int radius, float min_rel,
                       void *stream);
+// k_stream_peaks / k_ls_stream (tdoa_stream_peaks): k_peaks and the per-peak
+// refinement over the frames a streaming step listed -- the batch size is
+// *count (device, clamped to [0, S]), slot i's score block is
+// est + ids[i] * P * K, output row i; gate (optional, device [S]): a slot whose
+// byte is 0 gets the empty record
+int tdoa_launch_stream_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const void *est,
+                             bool is_float, const int32_t *ids, const int32_t *count, const uint8_t *gate,
+                             int64_t S, int num_peaks, int radius, float min_rel, void *stream);
+int tdoa_launch_ls_stream(const tdoa_kparams &kp, const void *est, bool is_float, const int32_t *ids,
+                          const int32_t *count, int64_t S, const int32_t *lags, const int32_t *cells,
+                          float *xy_ls, float *rms, int per_frame, void *stream);
 size_t tdoa_stream_trigger_lds(int M, int N, int H);
 // The hop's frame selectors.  Each lists the frames it chooses as sp.ids[slot],
 // sp.end[slot] (>= N: no frame reaches before its stream's start) and

@@ -82,63 +82,44 @@ __global__ void __launch_bounds__(128) k_ls(tdoa_kparams kp, const T *__restrict
         for (int p = 0; p < P; p++)  // ... or from the raw scores
             tau[p] = ls_tau(scores + ((size_t)f * P + p) * K, K, lags[f * P + p]);
     }
-    int cell = cells[f];
-    cell = cell < 0 ? 0 : (cell >= kp.G ? kp.G - 1 : cell);
-    const double sc = (double)kp.grid_scale;
-    double u = (double)(cell % kp.grid_W - kp.half_w) / sc;
-    double v = (double)(kp.half_h - cell / kp.grid_W) / sc;
-    const double lu = (double)kp.half_w / sc, lv = (double)kp.half_h / sc;
-    const double h = (double)kp.height, kf = (double)kp.fs / (double)kp.c;
-    double ss = 0.0;
-    for (int it = 0; it <= iters; it++) {
-        const double n2 = u * u + v * v + h * h, n = sqrt(n2), n3 = n2 * n;
-        const double k = h / n;
-        const double px = k * u, py = k * v, pz = k * h;
-        const double dxu = h * (1.0 / n - u * u / n3), dyu = h * (-v * u / n3),
-                     dzu = h * (-h * u / n3);
-        const double dxv = h * (-u * v / n3), dyv = h * (1.0 / n - v * v / n3),
-                     dzv = h * (-h * v / n3);
-        double d[M], du[M], dv[M];
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            const double ex = px - (double)kp.mic_xy[2 * m], ey = py - (double)kp.mic_xy[2 * m + 1],
-                         ez = pz;
-            d[m] = sqrt(ex * ex + ey * ey + ez * ez);
-            du[m] = (ex * dxu + ey * dyu + ez * dzu) / d[m];
-            dv[m] = (ex * dxv + ey * dyv + ez * dzv) / d[m];
+#include "tdoa_ls_solve.inc"
+}
+
+// tdoa_stream_peaks: row f is peak f % per_frame of the step's slot
+// f / per_frame, whose score block is est + ids[slot] * P * K; rows of slots
+// >= the step's count (read here, clamped as k_stream_peaks clamps it) are
+// not written.  An empty slot (cell < 0) gets NaN.
+template <typename T, int MM>
+__global__ void __launch_bounds__(128) k_ls_stream(tdoa_kparams kp, const T *__restrict__ est,
+                                                   const int32_t *__restrict__ ids,
+                                                   const int32_t *__restrict__ count, int nstreams,
+                                                   const int32_t *__restrict__ lags,
+                                                   const int32_t *__restrict__ cells,
+                                                   float *__restrict__ xy_ls, float *__restrict__ rms_out,
+                                                   int iters, int per_frame)
+{
+    const int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int cnt_raw = *count;
+    const int cnt = cnt_raw < 0 ? 0 : (cnt_raw > nstreams ? nstreams : cnt_raw);
+    if (f >= (int64_t)cnt * per_frame)
+        return;
+    constexpr int M = MM, P = MM * (MM - 1) / 2;
+    const int K = kp.K;
+    if (cells[f] < 0) {
+        if (xy_ls) {
+            xy_ls[2 * f] = NAN;
+            xy_ls[2 * f + 1] = NAN;
         }
-        double a11 = 0.0, a12 = 0.0, a22 = 0.0, g1 = 0.0, g2 = 0.0;
-        ss = 0.0;
-        int p = 0;  // pairs (i, j), i < j, in the context's (lexicographic) order
-#pragma unroll
-        for (int i = 0; i < M; i++)
-#pragma unroll
-            for (int j = i + 1; j < M; j++, p++) {
-                const double r = (d[j] - d[i]) * kf - tau[p];
-                const double ju = (du[j] - du[i]) * kf, jv = (dv[j] - dv[i]) * kf;
-                a11 += ju * ju;
-                a12 += ju * jv;
-                a22 += jv * jv;
-                g1 += ju * r;
-                g2 += jv * r;
-                ss += r * r;
-            }
-        if (it == iters)
-            break;
-        const double lam = 1e-3 * (a11 + a22) + 1e-12;
-        const double b11 = a11 + lam, b22 = a22 + lam;
-        const double det = b11 * b22 - a12 * a12;
-        u -= (b22 * g1 - a12 * g2) / det;
-        v -= (b11 * g2 - a12 * g1) / det;
-        u = u < -lu ? -lu : (u > lu ? lu : u);
-        v = v < -lv ? -lv : (v > lv ? lv : v);
+        if (rms_out)
+            rms_out[f] = NAN;
+        return;
     }
-    if (xy_ls) {
-        xy_ls[2 * f] = (float)u;
-        xy_ls[2 * f + 1] = (float)v;
-    }
-    if (rms_out)
-        rms_out[f] = (float)sqrt(ss / (double)P);
+    double tau[P];
+    const T *sf = est + (size_t)ids[f / per_frame] * P * K;
+#pragma unroll
+    for (int p = 0; p < P; p++)
+        tau[p] = ls_tau(sf + (size_t)p * K, K, lags[f * P + p]);
+#include "tdoa_ls_solve.inc"
 }
 
 }  // namespace
@@ -189,6 +170,51 @@ int tdoa_launch_ls(const tdoa_kparams &kp, const void *scores, bool is_float, co
     if (e != hipSuccess) {
         char buf[256];
         snprintf(buf, sizeof buf, "k_ls launch: %s", hipGetErrorString(e));
+        return tdoa_set_error(-2, buf);
+    }
+    return 0;
+}
+
+int tdoa_launch_ls_stream(const tdoa_kparams &kp, const void *est, bool is_float, const int32_t *ids,
+                          const int32_t *count, int64_t S, const int32_t *lags, const int32_t *cells,
+                          float *xy_ls, float *rms, int per_frame, void *stream)
+{
+    if (S <= 0 || per_frame <= 0)
+        return 0;
+    // one thread per row of every slot the step can list; those past its count return
+    const int64_t grid = (S * per_frame + 127) / 128;
+    if (S > 0x7fffffff || grid > 0x7fffffff)
+        return tdoa_set_error(-1, "ls: too many streams for one launch");
+    if (!est || !ids || !count || !lags || !cells)
+        return tdoa_set_error(-1, "ls: per-slot rows read the state, the step's list and the peaks");
+    hipStream_t st = (hipStream_t)stream;
+#define TDOA_LS_S(TT, MM)                                                                              \
+    hipLaunchKernelGGL((k_ls_stream<TT, MM>), dim3((unsigned)grid), dim3(128), 0, st, kp, (const TT *)est, \
+                       ids, count, (int)S, lags, cells, xy_ls, rms, TDOA_LS_ITERS, per_frame)
+#define TDOA_LS_M(MM)                \
+    case MM:                         \
+        if (is_float)                \
+            TDOA_LS_S(float, MM);    \
+        else                         \
+            TDOA_LS_S(int64_t, MM);  \
+        break
+    switch (kp.M) {
+        TDOA_LS_M(2);
+        TDOA_LS_M(3);
+        TDOA_LS_M(4);
+        TDOA_LS_M(5);
+        TDOA_LS_M(6);
+        TDOA_LS_M(7);
+        TDOA_LS_M(8);
+    default:
+        return tdoa_set_error(-1, "ls: num_mics outside 2..8");
+    }
+#undef TDOA_LS_M
+#undef TDOA_LS_S
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "k_ls_stream launch: %s", hipGetErrorString(e));
         return tdoa_set_error(-2, buf);
     }
     return 0;

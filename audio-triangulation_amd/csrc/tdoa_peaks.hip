@@ -68,123 +68,63 @@ __global__ void __launch_bounds__(PEAKS_MAX_THREADS) k_peaks(tdoa_kparams kp, td
                                                          int radius, float min_rel)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int P = kp.P, K = kp.K, G = kp.G, GW = kp.grid_W, GH = G / GW, PK = P * K;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nth = blockDim.x;
-    const int nwaves = nth >> 6, NS = (G + 31) >> 5;
-    T *W = (T *)smem;
-    T *Lmap = W + PK;
-    T *redv = Lmap + G;
-    int *redi = (int *)(redv + nwaves);
-    uint32_t *sup = (uint32_t *)(redi + nwaves);
     const int64_t f = blockIdx.x;
+    const uint8_t *const lut = kp.lut;
+#define PEAKS_FRAME_SRC (scores + f * PK)
+#include "tdoa_peaks_frame.inc"
+#undef PEAKS_FRAME_SRC
+}
 
-    const T *src = scores + f * PK;
-    for (int e = tid; e < PK; e += nth)
-        W[e] = src[e];
-    for (int e = tid; e < NS; e += nth)
-        sup[e] = 0u;
-    __syncthreads();
-    // the L map: LUT bytes from global memory (coalesced over c), scores gathered
-    // from LDS; one add per pair in ascending p, no reassociation
-    for (int c = tid; c < G; c += nth) {
-        T L = 0;
-        for (int p = 0; p < P; p++) {
-            int k = kp.lut[(size_t)p * G + c];
-            k = k < K ? k : K - 1;  // the context's LUT never exceeds it
-            L += W[p * K + k];
-        }
-        Lmap[c] = L;
-    }
-    __syncthreads();
-
-    int count = 0;
-    int my_cell = -1;         // thread k keeps peak k
-    T my_val = lowest_t<T>();
-    T v0 = lowest_t<T>();
-    for (int k = 0; k < Kp; k++) {
-        T bv = lowest_t<T>();
-        int bu = INT_MAX;
-        // increasing c per thread: strict '>' keeps the first; the first
-        // unsuppressed cell is taken whatever its value.  PEAKS_SCAN cells'
-        // reads (clamped, so unconditional) are issued before the first compare:
-        // one cell at a time waited for the bit, then for the value.
-        for (int c0 = tid; c0 < G; c0 += PEAKS_SCAN * nth) {
-            T v[PEAKS_SCAN];
-            uint32_t s[PEAKS_SCAN];
-#pragma unroll
-            for (int i = 0; i < PEAKS_SCAN; i++) {
-                const int c = c0 + i * nth, cc = c < G ? c : G - 1;
-                v[i] = Lmap[cc];
-                s[i] = sup[cc >> 5];
-            }
-#pragma unroll
-            for (int i = 0; i < PEAKS_SCAN; i++) {
-                const int c = c0 + i * nth;
-                const bool here = c < G && !((s[i] >> (c & 31)) & 1u);
-                if (here && (v[i] > bv || bu == INT_MAX)) {
-                    bv = v[i];
-                    bu = c;
+// tdoa_stream_peaks: the peaks of the EMA map of every frame a streaming step
+// listed.  The batch is the step's: `count_dev` is its counter slot (clamped to
+// [0, nstreams] as the hop kernels clamp it), ids[slot] the stream of slot
+// `slot`, whose score block is est + ids[slot] * P * K; output row = slot.
+// Workgroups are persistent over the slots.  A slot whose gate byte is 0 gets
+// the empty record without its map being evaluated (gate may be null: every
+// slot is evaluated).  The LUT is read from global memory as k_peaks reads it:
+// staged once per workgroup in LDS it measured slower at 3 mics float, the one
+// shape where it fits beside the map with two workgroups per CU (48.0 vs
+// 40.7 ns per frame at num_peaks 4, 20.9 vs 18.9 at 1; DESIGN.md, k_stream_peaks).
+template <typename T>
+__global__ void __launch_bounds__(PEAKS_MAX_THREADS) k_stream_peaks(
+    tdoa_kparams kp, tdoa_peaks_kout out, const T *__restrict__ est, const int32_t *__restrict__ ids,
+    const int32_t *__restrict__ count_dev, const uint8_t *__restrict__ gate, int nstreams, int Kp, int radius,
+    float min_rel)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int P = kp.P, tid = threadIdx.x;
+    const int cnt_raw = *count_dev;
+    const int cnt = cnt_raw < 0 ? 0 : (cnt_raw > nstreams ? nstreams : cnt_raw);
+    if ((int)blockIdx.x >= cnt)
+        return;
+    const uint8_t *const lut = kp.lut;
+    int s = ids[blockIdx.x];
+    for (int slot = blockIdx.x; slot < cnt; slot += gridDim.x) {
+        // the next slot's stream now: its load is off the next frame's path to the scores
+        const int stream = s, nxt = slot + (int)gridDim.x;
+        s = nxt < cnt ? ids[nxt] : 0;
+        if (gate && !gate[slot]) {  // the same byte for every thread
+            if (tid < Kp) {
+                const int64_t i = (int64_t)slot * Kp + tid;
+                out.cell[i] = -1;
+                store_L<T>(out, i, lowest_t<T>());
+                if (out.xy) {
+                    out.xy[2 * i] = NAN;
+                    out.xy[2 * i + 1] = NAN;
                 }
+                if (out.lags)
+                    for (int p = 0; p < P; p++)
+                        out.lags[i * P + p] = 0;
             }
+            if (tid == 0 && out.count)
+                out.count[slot] = 0;
+            continue;
         }
-        for (int m = 32; m >= 1; m >>= 1)
-            better_t(bv, bu, __shfl_xor(bv, m, 64), __shfl_xor(bu, m, 64));
-        if (lane == 0) {
-            redv[wave] = bv;
-            redi[wave] = bu;
-        }
-        __syncthreads();
-        bv = redv[0];
-        bu = redi[0];
-        for (int w = 1; w < nwaves; w++)
-            better_t(bv, bu, redv[w], redi[w]);
-        // every thread holds the same (bv, bu): the decisions below are uniform
-        if (bu < 0 || bu >= G)  // no cell remains
-            break;
-        if (k == 0)
-            v0 = bv;
-        else if (min_rel > 0.0f && !((double)bv >= (double)min_rel * (double)v0))
-            break;
-        if (tid == k) {
-            my_cell = bu;
-            my_val = bv;
-        }
-        count = k + 1;
-        if (k + 1 == Kp)
-            break;
-        // suppress the peak's square, clipped to the grid
-        const int px = bu % GW, py = bu / GW;
-        const int x0 = px - radius > 0 ? px - radius : 0;
-        const int x1 = px + radius < GW - 1 ? px + radius : GW - 1;
-        const int y0 = py - radius > 0 ? py - radius : 0;
-        const int y1 = py + radius < GH - 1 ? py + radius : GH - 1;
-        const int sw = x1 - x0 + 1, n = sw * (y1 - y0 + 1);
-        for (int e = tid; e < n; e += nth) {
-            const int dy = e / sw, dx = e - dy * sw;
-            const int c = (y0 + dy) * GW + x0 + dx;
-            atomicOr(&sup[c >> 5], 1u << (c & 31));
-        }
-        __syncthreads();  // the bits are set, and redv / redi are free again
+        const int64_t f = slot;
+#define PEAKS_FRAME_SRC (est + (int64_t)stream * PK)
+#include "tdoa_peaks_frame.inc"
+#undef PEAKS_FRAME_SRC
     }
-
-    // one thread per slot writes the peak, or the empty slot's fills
-    if (tid < Kp) {
-        const int64_t i = f * Kp + tid;
-        const bool have = tid < count;
-        const int cell = have ? my_cell : -1;
-        out.cell[i] = cell;
-        store_L<T>(out, i, have ? my_val : lowest_t<T>());
-        if (out.xy) {
-            const int cx = have ? cell % GW : 0, cy = have ? cell / GW : 0;
-            out.xy[2 * i] = have ? (float)(cx - kp.half_w) / kp.grid_scale : NAN;
-            out.xy[2 * i + 1] = have ? (float)(kp.half_h - cy) / kp.grid_scale : NAN;
-        }
-        if (out.lags)
-            for (int p = 0; p < P; p++)
-                out.lags[i * P + p] = have ? (int)kp.lut[(size_t)p * G + cell] - kp.S : 0;
-    }
-    if (tid == 0 && out.count)
-        out.count[f] = count;
 }
 
 template <typename T>
@@ -240,4 +180,50 @@ int tdoa_launch_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const 
     const int th = lds > 80 * 1024 ? 1024 : 512;
     return is_float ? launch<float>(kp, out, (const float *)scores, B, num_peaks, radius, min_rel, th, lds, st)
                     : launch<int64_t>(kp, out, (const int64_t *)scores, B, num_peaks, radius, min_rel, th, lds, st);
+}
+
+namespace {
+
+template <typename T>
+void launch_stream(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const T *est, const int32_t *ids,
+                   const int32_t *count, const uint8_t *gate, int64_t S, int Kp, int radius, float min_rel,
+                   int threads, size_t lds, hipStream_t st)
+{
+    // as many workgroups as are resident at this LDS, at most one per stream
+    const int res = tdoa_resident_blocks((const void *)k_stream_peaks<T>, threads, lds);
+    const unsigned grid = (unsigned)(S < res ? S : res);
+    hipLaunchKernelGGL(k_stream_peaks<T>, dim3(grid), dim3(threads), lds, st, kp, out, est, ids, count, gate,
+                       (int)S, Kp, radius, min_rel);
+}
+
+}  // namespace
+
+int tdoa_launch_stream_peaks(const tdoa_kparams &kp, const tdoa_peaks_kout &out, const void *est,
+                             bool is_float, const int32_t *ids, const int32_t *count, const uint8_t *gate,
+                             int64_t S, int num_peaks, int radius, float min_rel, void *stream)
+{
+    if (S <= 0)
+        return 0;
+    if (S > INT_MAX)
+        return tdoa_set_error(-1, "stream peaks: too many streams for one launch");
+    if (!tdoa_peaks_fits(kp, is_float))
+        return tdoa_set_error(-1, "stream peaks: the L map and one frame's scores exceed the LDS budget");
+    const int span = kp.grid_W > kp.G / kp.grid_W ? kp.grid_W : kp.G / kp.grid_W;
+    if (radius > span)  // as tdoa_launch_peaks
+        radius = span;
+    const size_t lds = tdoa_peaks_lds(kp, is_float);
+    const int th = lds > 80 * 1024 ? 1024 : 512;  // tdoa_launch_peaks' rule
+    hipStream_t st = (hipStream_t)stream;
+    if (is_float)
+        launch_stream<float>(kp, out, (const float *)est, ids, count, gate, S, num_peaks, radius, min_rel, th, lds, st);
+    else
+        launch_stream<int64_t>(kp, out, (const int64_t *)est, ids, count, gate, S, num_peaks, radius, min_rel, th,
+                               lds, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        char buf[256];
+        snprintf(buf, sizeof buf, "k_stream_peaks launch: %s", hipGetErrorString(e));
+        return tdoa_set_error(-2, buf);
+    }
+    return 0;
 }

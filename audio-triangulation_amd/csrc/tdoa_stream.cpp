@@ -61,6 +61,7 @@ struct tdoa_stream {
     tdoa_kparams kp;
     tdoa_stream_params sp;
     tdoa_devmem mem;  // one allocation for all state
+    tdoa_devmem peak_lags;  // tdoa_stream_peaks: [S][TDOA_MAX_PEAKS][P] lag tuples when only the refinement reads them
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
     step_graph g[2];  // one per counter parity; released before mem
@@ -430,6 +431,62 @@ extern "C" int tdoa_stream_state_f(tdoa_stream *st, int64_t *pos, float *est, ui
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_state_f: a DIRECT pipeline's scores are int64 "
                                            "(tdoa_stream_state)");
     return stream_state(st, pos, est, last, stats);
+}
+
+extern "C" int tdoa_stream_peaks(tdoa_stream *st, const tdoa_peaks_params *prm, const uint8_t *gate,
+                                 const tdoa_peaks_outputs *out, void *stream)
+{
+    if (!st || !prm || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_peaks: NULL argument");
+    if (!out->cell)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_peaks: outputs.cell is required");
+    if (prm->num_peaks < 1 || prm->num_peaks > TDOA_MAX_PEAKS)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_peaks: num_peaks %d outside 1..%d", (int)prm->num_peaks,
+                         TDOA_MAX_PEAKS);
+    if (prm->radius < 0)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_peaks: negative radius");
+    if (!tdoa_peaks_fits(st->kp, st->phat))
+        return tdoa_fail(TDOA_ERR_INVALID,
+                         "tdoa_stream_peaks: the L map and one stream's scores (%zu bytes) exceed the LDS budget",
+                         tdoa_peaks_lds(st->kp, st->phat));
+    if (st->hop == 0)  // no step since creation or reset: no list to read
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(st->device));
+    const int Kp = prm->num_peaks, P = st->kp.P;
+    const bool ls = out->xy_ls || out->ls_rms;
+    tdoa_peaks_kout k;
+    k.count = out->count;
+    k.cell = out->cell;
+    k.xy = out->xy;
+    k.L = st->phat ? nullptr : out->L;  // the pipeline's type decides which is written
+    k.Lf = st->phat ? out->Lf : nullptr;
+    k.lags = out->lags;
+    if (ls && !k.lags) {
+        // the refinement reads each peak's lag tuple: one scratch for every Kp, made once
+        const size_t need = (size_t)st->S * TDOA_MAX_PEAKS * P * sizeof(int32_t);
+        if (!st->peak_lags && st->peak_lags.alloc(need) != hipSuccess)
+            return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_peaks: peak-lag scratch of %zu bytes", need);
+        k.lags = st->peak_lags.get<int32_t>();
+    }
+    // the last step's counter slot and list: both hold until the next step,
+    // whose selector zeroes that slot (its count_next) and writes a new list
+    const int32_t *count = st->sp.count + (int)((st->hop - 1) & 1);
+    const void *est = st->phat ? (const void *)st->est_f : (const void *)st->sp.est;
+    int rc = tdoa_launch_stream_peaks(st->kp, k, est, st->phat, st->sp.ids, count, gate, st->S, Kp, prm->radius,
+                                      prm->min_rel, stream);
+    if (rc != 0 || !ls)
+        return rc;
+    return tdoa_launch_ls_stream(st->kp, est, st->phat, st->sp.ids, count, st->S, k.lags, k.cell, out->xy_ls,
+                                 out->ls_rms, Kp, stream);
+}
+
+extern "C" int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is_float)
+{
+    if (!st || !est || !is_float)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_est_device: NULL argument");
+    *est = st->phat ? (const void *)st->est_f : (const void *)st->sp.est;
+    *is_float = st->phat ? 1 : 0;
+    return TDOA_OK;
 }
 
 extern "C" int tdoa_stream_destroy(tdoa_stream *st)

@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_batch_grid_fused", "tdoa_gpu_clock_mhz",
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f", "tdoa_stream_create_pcm16",
-    "tdoa_stream_create_continuous",
+    "tdoa_stream_create_continuous", "tdoa_stream_peaks", "tdoa_stream_est_device",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -165,6 +165,8 @@ def load() -> C.CDLL:
     L.tdoa_stream_step_f.argtypes = [P, C.POINTER(StreamOutputsF), P]
     L.tdoa_stream_state_f.argtypes = [P, P, P, P, P]
     L.tdoa_stream_destroy.argtypes = [P]
+    L.tdoa_stream_peaks.argtypes = [P, C.POINTER(PeaksParams), P, C.POINTER(PeaksOutputs), P]
+    L.tdoa_stream_est_device.argtypes = [P, C.POINTER(P), C.POINTER(C.c_int)]
     L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
     L.tdoa_set_bin_weights.argtypes = [P, P]
     L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]

@@ -20,6 +20,12 @@ threshold `trigger_var` (counts^2, default 131072 = 2 * 256^2, the 8-bit
 trigger for samples scaled by 256).  The pipeline keeps the format it was
 created in.
 
+peaks() / peak_records() report, per hop and without a host synchronisation,
+up to `num_peaks` maxima of the EMA map of every frame the step listed
+(tdoa_stream_peaks: k_stream_peaks, with ls the per-peak least-squares
+refinement k_ls_stream); peaks_all() runs tdoa_peaks over the whole device
+state, est_ptr() hands that state out as a device address.
+
 mode="continuous" (a `gcc_phat` Localizer; tdoa_stream_create_continuous:
 k_stream_active in place of a trigger) chooses frames for continuous audio
 instead of clicks.  The ring is uint8 or int16 according to loc.sample_format.
@@ -38,7 +44,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import STREAM_TRIGGER_VAR_PCM16, StreamOutputs, StreamOutputsF, check, load
+from ._lib import (STREAM_TRIGGER_VAR_PCM16, PeaksOutputs, PeaksParams, StreamOutputs, StreamOutputsF, check,
+                   load)
 from .localizer import Localizer
 
 
@@ -120,6 +127,8 @@ class StreamPipeline:
                                             self.capture_len, int(use_graph), C.byref(h)),
                   "tdoa_stream_create")
         self._h = h
+        self._peaks = {}  # (Kp, ls) -> the output tensors of peaks()
+        self._peaks_last = None
 
     def step(self) -> dict:
         """One hop for every stream (asynchronous on self.stream)."""
@@ -134,6 +143,92 @@ class StreamPipeline:
         r = {k: v[:n].cpu().numpy() for k, v in self.out.items() if k != "count"}
         order = np.argsort(r["stream_id"], kind="stable")
         return {k: v[order] for k, v in r.items()}
+
+    def peaks(self, num_peaks: int = 2, radius: int = 8, min_rel: float = 0.0, ls: bool = False,
+              gated_only: bool = True) -> dict:
+        """Up to `num_peaks` maxima of the EMA map of every frame the last step
+        listed (tdoa_stream_peaks), asynchronous on self.stream: call it after
+        step() and before the next one.
+
+        Returns device tensors indexed by the step's slots, rows < out["count"]
+        written: count [S], cell [S][Kp] (-1 in empty slots), xy [S][Kp][2], L
+        (DIRECT, int64) or Lf (GCC_PHAT, float32) [S][Kp], lags [S][Kp][P] and,
+        with ls, xy_ls [S][Kp][2] / ls_rms [S][Kp].  They are allocated once per
+        (num_peaks, ls) and reused by later calls.  gated_only: slots whose frame
+        did not pass the gate (out["gate"] == 0) get the empty record; otherwise
+        every listed slot's map is searched, as its last gated frame left it."""
+        Kp, ls = int(num_peaks), bool(ls)
+        o = self._peaks.get((Kp, ls))
+        if o is None:
+            S, n, P, dev = self.S, max(Kp, 0), self.loc.dims.P, self.loc.torch_device
+            o = {"count": torch.zeros(S, dtype=torch.int32, device=dev),
+                 "cell": torch.zeros((S, n), dtype=torch.int32, device=dev),
+                 "xy": torch.zeros((S, n, 2), dtype=torch.float32, device=dev),
+                 "Lf" if self.phat else "L": torch.zeros((S, n), dtype=torch.float32 if self.phat else torch.int64,
+                                                         device=dev),
+                 "lags": torch.zeros((S, n, P), dtype=torch.int32, device=dev)}
+            if ls:
+                o["xy_ls"] = torch.zeros((S, n, 2), dtype=torch.float32, device=dev)
+                o["ls_rms"] = torch.zeros((S, n), dtype=torch.float32, device=dev)
+            # the allocator's fills ran on the current stream: they precede the kernels on self.stream
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+        prm = PeaksParams(Kp, int(radius), float(min_rel))
+        s = PeaksOutputs()
+        for name, _ in PeaksOutputs._fields_:
+            t = o.get(name)
+            setattr(s, name, t.data_ptr() if t is not None and t.numel() else None)
+        gate = C.c_void_p(self.out["gate"].data_ptr()) if gated_only else None
+        check(load().tdoa_stream_peaks(self._h, C.byref(prm), gate, C.byref(s), C.c_void_p(self.stream.cuda_stream)),
+              "tdoa_stream_peaks")
+        self._peaks[(Kp, ls)] = o  # kept only once the library accepted the arguments
+        self._peaks_last = o
+        return o
+
+    def peak_records(self) -> dict:
+        """Synchronously fetch the last peaks() call's rows of this step's slots,
+        sorted by stream, with the slots' stream_id attached."""
+        if self._peaks_last is None:
+            raise RuntimeError("peak_records() reads the result of a peaks() call")
+        self.stream.synchronize()
+        n = int(self.out["count"].item())
+        r = {k: v[:n].cpu().numpy() for k, v in self._peaks_last.items()}
+        r["stream_id"] = self.out["stream_id"][:n].cpu().numpy()
+        order = np.argsort(r["stream_id"], kind="stable")
+        return {k: v[order] for k, v in r.items()}
+
+    def est_ptr(self):
+        """(device address, is_float) of the EMA state: int64 [S][P][K] (DIRECT)
+        or float32 [S][P][K] (GCC_PHAT); valid until close().  Calls that read
+        it are stream-ordered with the steps (tdoa_stream_est_device)."""
+        ptr, flt = C.c_void_p(), C.c_int()
+        check(load().tdoa_stream_est_device(self._h, C.byref(ptr), C.byref(flt)), "tdoa_stream_est_device")
+        return int(ptr.value), bool(flt.value)
+
+    def peaks_all(self, num_peaks: int = 2, radius: int = 8, min_rel: float = 0.0, ls: bool = False) -> dict:
+        """tdoa_peaks over the whole device state, one row per stream (B = S),
+        listed or not, asynchronous on self.stream; fresh tensors as
+        Localizer.peaks returns them."""
+        S, Kp, P, dev = self.S, int(num_peaks), self.loc.dims.P, self.loc.torch_device
+        n = max(Kp, 0)
+        with torch.cuda.stream(self.stream):
+            o = {"count": torch.empty(S, dtype=torch.int32, device=dev),
+                 "cell": torch.empty((S, n), dtype=torch.int32, device=dev),
+                 "xy": torch.empty((S, n, 2), dtype=torch.float32, device=dev),
+                 "Lf" if self.phat else "L": torch.empty((S, n), dtype=torch.float32 if self.phat else torch.int64,
+                                                         device=dev),
+                 "lags": torch.empty((S, n, P), dtype=torch.int32, device=dev)}
+            if ls:
+                o["xy_ls"] = torch.empty((S, n, 2), dtype=torch.float32, device=dev)
+                o["ls_rms"] = torch.empty((S, n), dtype=torch.float32, device=dev)
+        ptr, flt = self.est_ptr()
+        prm = PeaksParams(Kp, int(radius), float(min_rel))
+        s = PeaksOutputs()
+        for name, _ in PeaksOutputs._fields_:
+            t = o.get(name)
+            setattr(s, name, t.data_ptr() if t is not None and t.numel() else None)
+        check(load().tdoa_peaks(self.loc._ctx, C.c_void_p(ptr), int(flt), S, C.byref(prm), C.byref(s),
+                                C.c_void_p(self.stream.cuda_stream)), "tdoa_peaks")
+        return o
 
     def reset(self) -> None:
         check(load().tdoa_stream_reset(self._h, C.c_void_p(self.stream.cuda_stream)),

@@ -477,6 +477,62 @@ int tdoa_stream_state(tdoa_stream *st, int64_t *pos, int64_t *est, uint64_t *las
                       int64_t *stats);
 int tdoa_stream_state_f(tdoa_stream *st, int64_t *pos, float *est, uint64_t *last,
                         int64_t *stats);
+
+/* ---- Streaming: peaks and least-squares refinement of the EMA map per hop ----
+ * The EMA state est[S][P][K] of a pipeline is the time-averaged map tdoa_peaks
+ * names among its inputs; several sources accumulate in it over hops.
+ * tdoa_stream_peaks runs tdoa_peaks on it for the frames the pipeline's last
+ * step listed, without a host synchronisation or a copy.
+ *
+ * Let h be the step enqueued last on st since its creation or last reset; if
+ * there is none, nothing is launched and the call returns TDOA_OK.  Let cnt be
+ * h's frame count as the hop kernels clamp it, to [0, S], and for slot i < cnt
+ * let s be the stream the pipeline listed in slot i (its own list, the one the
+ * step copies to stream_id, not a caller buffer).  Row i of every output is
+ * the tdoa_peaks result for the single block est[s] as step h left it, in the
+ * pipeline's type (L for DIRECT, Lf for GCC_PHAT; the other field is not
+ * written), by tdoa_peaks' own definition: the L map in T with one add per pair
+ * in ascending p, greedy suppression, ties to the lowest cell, min_rel, the
+ * empty-slot fills.  Outputs are [S][Kp]..., indexed by slot; rows >= cnt are
+ * not written, and a hop with cnt = 0 writes nothing.
+ *
+ * gate, if non-NULL, is the step's gate output (device [S]): a slot with
+ * gate[i] == 0 gets the empty record -- count[i] = 0 and every peak slot filled
+ * as empty (cell -1, xy NaN, L INT64_MIN / Lf -inf, lags 0, xy_ls / ls_rms
+ * NaN) -- and its map is not evaluated.  With gate == NULL every listed slot is
+ * evaluated, gated or not: the map of a stream whose frame was not gated is
+ * the one its last gated frame left.  A stream never updated has an all-zero
+ * map: peak 0 is cell 0 with L = 0 (and with radius < the grid further peaks
+ * follow, all with L = 0).
+ *
+ * xy_ls / ls_rms: as in tdoa_peaks, the refinement started at each peak with
+ * the peak's lag tuple and the parabolic vertex of est[s] at those lags (the
+ * int64 values read exactly); NaN in empty slots.
+ *
+ * Asynchronous on `stream`; never synchronises the host; plain launches
+ * (k_stream_peaks, k_ls_stream) whether or not the pipeline replays graphs.
+ * The call must be stream-ordered after step h and before the pipeline's next
+ * step: the next step's selector writes a new list and zeroes h's counter slot
+ * (the two slots alternate by hop parity, so h's is reused two steps later).
+ * The one allocation, made at the first call that asks for xy_ls / ls_rms
+ * without out->lags and never again, is a lag-tuple scratch of
+ * S * TDOA_MAX_PEAKS * P int32 owned by st.
+ *
+ * TDOA_ERR_INVALID, with tdoa_last_error naming the cause: a NULL st / prm /
+ * out / out->cell (checked before any device call), num_peaks outside
+ * 1..TDOA_MAX_PEAKS, radius < 0, or a grid whose L map plus one stream's scores
+ * exceed k_peaks' 150 KiB of LDS for the pipeline's type.  Nothing is launched
+ * and no output is touched. */
+int tdoa_stream_peaks(tdoa_stream *st, const tdoa_peaks_params *prm,
+                      const uint8_t *gate /* device [S] or NULL */,
+                      const tdoa_peaks_outputs *out, void *stream);
+/* The pipeline's EMA state as a device pointer: int64 [S][P][K] (DIRECT,
+ * *is_float = 0) or float [S][P][K] (GCC_PHAT, 1).  Valid until
+ * tdoa_stream_destroy.  It makes the whole state usable with what exists --
+ * tdoa_peaks(ctx, est, is_float, S, ...) and tdoa_heatmap for every stream,
+ * not only the listed ones; such calls follow the usual rule: stream-ordered
+ * with the steps.  Host only; TDOA_ERR_INVALID for a NULL argument. */
+int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is_float);
 int tdoa_stream_destroy(tdoa_stream *st);
 
 const char *tdoa_last_error(void);

@@ -24,6 +24,7 @@
 #include "../../include/tdoa.h"
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
+#include "tdoa_track_rule.h"
 
 // a step's outputs, either engine's: tdoa_stream_outputs with max_L null and
 // max_Lf set for a GCC_PHAT pipeline (tdoa_stream_outputs_f)
@@ -62,6 +63,7 @@ struct tdoa_stream {
     tdoa_stream_params sp;
     tdoa_devmem mem;  // one allocation for all state
     tdoa_devmem peak_lags;  // tdoa_stream_peaks: [S][TDOA_MAX_PEAKS][P] lag tuples when only the refinement reads them
+    tdoa_devmem track_mem;  // tdoa_stream_track: tracks [S][TDOA_MAX_TRACKS], then next_id [S]
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
     step_graph g[2];  // one per counter parity; released before mem
@@ -384,6 +386,8 @@ extern "C" int tdoa_stream_reset(tdoa_stream *st, void *stream)
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_reset: NULL stream");
     HIP_TRY(hipSetDevice(st->device));
     HIP_TRY(hipMemsetAsync(st->mem.get<void>(), 0, st->mem.bytes(), (hipStream_t)stream));
+    if (st->track_mem)  // no tracks, ids from 1 again
+        HIP_TRY(hipMemsetAsync(st->track_mem.get<void>(), 0, st->track_mem.bytes(), (hipStream_t)stream));
     st->hop = 0;  // both counter slots are zero again
     return TDOA_OK;
 }
@@ -486,6 +490,46 @@ extern "C" int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_est_device: NULL argument");
     *est = st->phat ? (const void *)st->est_f : (const void *)st->sp.est;
     *is_float = st->phat ? 1 : 0;
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_stream_track(tdoa_stream *st, const tdoa_track_params *prm, const int32_t *count,
+                                 const float *xy, int32_t Kp, const tdoa_track_outputs *out, void *stream)
+{
+    if (!st)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_track: NULL argument");
+    const int rc = tdoa_track_check("tdoa_stream_track", prm, out, count, xy, Kp, st->S);
+    if (rc)
+        return rc;
+    HIP_TRY(hipSetDevice(st->device));
+    const size_t S = (size_t)st->S;
+    if (!st->track_mem) {
+        // the one allocation, zeroed before anything else on `stream` reads it
+        const size_t need = S * (TDOA_MAX_TRACKS * sizeof(tdoa_track) + sizeof(int32_t));
+        if (st->track_mem.alloc(need) != hipSuccess)
+            return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_track: %zu bytes of track state", need);
+        if (hipMemsetAsync(st->track_mem.get<void>(), 0, need, (hipStream_t)stream) != hipSuccess) {
+            st->track_mem.release();
+            return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_track: clearing the track state failed");
+        }
+    }
+    if (st->hop == 0)  // no step since creation or reset: no list to read
+        return TDOA_OK;
+    tdoa_track *tracks = st->track_mem.get<tdoa_track>();
+    int32_t *next_id = reinterpret_cast<int32_t *>(tracks + S * TDOA_MAX_TRACKS);
+    // the last step's counter slot and lists, as tdoa_stream_peaks reads them
+    const int32_t *rows_dev = st->sp.count + (int)((st->hop - 1) & 1);
+    return tdoa_launch_track(tracks, next_id, st->S, rows_dev, st->sp.ids, nullptr, st->sp.end, st->sp.fs, count, xy,
+                             Kp, *prm, *out, stream);
+}
+
+extern "C" int tdoa_stream_tracks_device(tdoa_stream *st, const tdoa_track **tracks, const int32_t **next_id)
+{
+    if (!st || !tracks || !next_id)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_tracks_device: NULL argument");
+    const tdoa_track *t = st->track_mem ? st->track_mem.get<tdoa_track>() : nullptr;
+    *tracks = t;
+    *next_id = t ? reinterpret_cast<const int32_t *>(t + (size_t)st->S * TDOA_MAX_TRACKS) : nullptr;
     return TDOA_OK;
 }
 

@@ -7,13 +7,18 @@
 See include/tdoa.h for the C ABI and DESIGN.md for the kernels.
 """
 from ._lib import (ENGINE_DIRECT, ENGINE_GCC_PHAT, EXPORTED_SYMBOLS, LIB_PATH,  # noqa: F401
-                   TdoaError, band_weights, decay_us, dpss_q15, load)
+                   MAX_TRACKS, TRACK_DEFAULTS, TRACK_FIELDS, TdoaError, Track, TrackOutputs, TrackParams,
+                   band_weights, decay_us, dpss_q15, load, track_host, track_params)
 
-__all__ = ["Localizer", "TdoaError", "load", "dpss_q15", "decay_us", "band_weights"]
+__all__ = ["Localizer", "TdoaError", "load", "dpss_q15", "decay_us", "band_weights", "track_host", "track_params",
+           "TrackParams", "TrackOutputs", "TRACK_DTYPE"]
 
 
 def __getattr__(name):
     # torch-dependent pieces load lazily so the ABI helpers work without torch
+    if name == "TRACK_DTYPE":  # numpy loads lazily, as torch does
+        import numpy as np
+        return np.dtype(TRACK_FIELDS)
     if name == "Localizer":
         from .localizer import Localizer
         return Localizer

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f", "tdoa_stream_create_pcm16",
     "tdoa_stream_create_continuous", "tdoa_stream_peaks", "tdoa_stream_est_device",
+    "tdoa_track_batch", "tdoa_track_host", "tdoa_stream_track", "tdoa_stream_tracks_device",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -83,6 +84,57 @@ class PeaksOutputs(C.Structure):
     """struct tdoa_peaks_outputs (include/tdoa.h): device pointers."""
     _fields_ = [(n, C.c_void_p) for n in (
         "count", "cell", "xy", "L", "Lf", "lags", "xy_ls", "ls_rms")]
+
+
+MAX_TRACKS = 8  # TDOA_MAX_TRACKS
+
+
+class Track(C.Structure):
+    """struct tdoa_track (include/tdoa.h): one 64-byte track record."""
+    _fields_ = [("id", C.c_int32), ("status", C.c_int32), ("hits", C.c_int32), ("misses", C.c_int32),
+                ("x", C.c_float), ("y", C.c_float), ("vx", C.c_float), ("vy", C.c_float),
+                ("p00", C.c_float), ("p01", C.c_float), ("p11", C.c_float), ("peak", C.c_int32),
+                ("t_us", C.c_int64), ("upd_us", C.c_int64)]
+
+
+# the same record as a numpy structured dtype (the fields are naturally aligned: no padding)
+TRACK_FIELDS = [("id", "<i4"), ("status", "<i4"), ("hits", "<i4"), ("misses", "<i4"),
+                ("x", "<f4"), ("y", "<f4"), ("vx", "<f4"), ("vy", "<f4"),
+                ("p00", "<f4"), ("p01", "<f4"), ("p11", "<f4"), ("peak", "<i4"),
+                ("t_us", "<i8"), ("upd_us", "<i8")]
+TRACK_STATUS = {0: "free", 1: "tentative", 2: "confirmed"}
+
+
+class TrackParams(C.Structure):
+    """struct tdoa_track_params (include/tdoa.h).  Lengths in metres, times in
+    seconds (max_coast_us in microseconds): meas_var r is the variance of a peak
+    position (m^2), accel_psd q the power spectral density of the unmodelled
+    acceleration (m^2/s^3), init_vel_var the velocity variance of a newborn
+    track (m^2/s^2), gate_d2 the largest accepted |z - x|^2 / (p00 + r)."""
+    _fields_ = [("max_tracks", C.c_int32), ("confirm_hits", C.c_int32), ("max_misses", C.c_int32),
+                ("max_coast_us", C.c_int64), ("gate_d2", C.c_float), ("meas_var", C.c_float),
+                ("accel_psd", C.c_float), ("init_vel_var", C.c_float)]
+
+
+# defaults of the Python faces: a grid cell at the default scale is 1/24 m, so
+# r = 0.01 m^2 is a 10 cm (2.4-cell) standard deviation; a gate of 9 is 3 sigma
+TRACK_DEFAULTS = dict(max_tracks=8, confirm_hits=3, max_misses=5, max_coast_us=2_000_000, gate_d2=9.0,
+                      meas_var=0.01, accel_psd=1.0, init_vel_var=4.0)
+
+
+def track_params(**kw) -> TrackParams:
+    """TrackParams from TRACK_DEFAULTS overridden by keywords."""
+    bad = set(kw) - set(TRACK_DEFAULTS)
+    if bad:
+        raise TypeError(f"unknown track parameter(s) {sorted(bad)}")
+    v = {**TRACK_DEFAULTS, **kw}
+    return TrackParams(int(v["max_tracks"]), int(v["confirm_hits"]), int(v["max_misses"]), int(v["max_coast_us"]),
+                       float(v["gate_d2"]), float(v["meas_var"]), float(v["accel_psd"]), float(v["init_vel_var"]))
+
+
+class TrackOutputs(C.Structure):
+    """struct tdoa_track_outputs (include/tdoa.h): any may be NULL, not all."""
+    _fields_ = [(n, C.c_void_p) for n in ("tracks", "assigned", "num_confirmed")]
 
 
 class StreamOutputs(C.Structure):
@@ -167,6 +219,11 @@ def load() -> C.CDLL:
     L.tdoa_stream_destroy.argtypes = [P]
     L.tdoa_stream_peaks.argtypes = [P, C.POINTER(PeaksParams), P, C.POINTER(PeaksOutputs), P]
     L.tdoa_stream_est_device.argtypes = [P, C.POINTER(P), C.POINTER(C.c_int)]
+    track_tail = [P, I32, C.POINTER(TrackParams), C.POINTER(TrackOutputs)]  # xy, Kp, prm, out
+    L.tdoa_track_batch.argtypes = [C.c_int, P, P, I64, P, P, P] + track_tail + [P]
+    L.tdoa_track_host.argtypes = [P, P, I64, P, P, P] + track_tail
+    L.tdoa_stream_track.argtypes = [P, C.POINTER(TrackParams), P] + track_tail[:2] + [C.POINTER(TrackOutputs), P]
+    L.tdoa_stream_tracks_device.argtypes = [P, C.POINTER(P), C.POINTER(P)]
     L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
     L.tdoa_set_bin_weights.argtypes = [P, P]
     L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]
@@ -219,3 +276,48 @@ def band_weights(N: int, fs: int, lo: float, hi: float, taper: float = 0.0):
 
 def decay_us(now_us: int, last_us: int) -> float:
     return float(load().tdoa_decay_us(int(now_us), int(last_us)))
+
+
+def track_host(tracks, next_id, t_us, count, xy, stream_of_row=None, **params) -> dict:
+    """tdoa_track_host: the tracker's rule (include/tdoa.h, "Tracking") on numpy
+    arrays, no device.  tracks [S][8] TRACK_DTYPE and next_id [S] int32 are the
+    state, updated in place; t_us [rows] int64, count [rows] int32 and
+    xy [rows][Kp][2] float32 are the rows, row i being stream stream_of_row[i]
+    (None: stream i).  Returns tracks [rows][T], assigned [rows][Kp] and
+    num_confirmed [rows]."""
+    import numpy as np
+    dt = np.dtype(TRACK_FIELDS)
+    if not (isinstance(tracks, np.ndarray) and tracks.dtype == dt and tracks.ndim == 2
+            and tracks.shape[1] == MAX_TRACKS and tracks.flags.c_contiguous and tracks.flags.writeable):
+        raise ValueError(f"tracks must be a writable C-contiguous [S][{MAX_TRACKS}] array of TRACK_DTYPE")
+    S = tracks.shape[0]
+    if not (isinstance(next_id, np.ndarray) and next_id.dtype == np.int32 and next_id.shape == (S,)
+            and next_id.flags.c_contiguous and next_id.flags.writeable):
+        raise ValueError("next_id must be a writable int32 [S] array")
+    xy = np.ascontiguousarray(xy, np.float32)
+    if xy.ndim != 3 or xy.shape[2] != 2:
+        raise ValueError("xy must be [rows][Kp][2]")
+    rows, Kp = xy.shape[0], xy.shape[1]
+    t_us = np.ascontiguousarray(t_us, np.int64)
+    count = np.ascontiguousarray(count, np.int32)
+    if t_us.shape != (rows,) or count.shape != (rows,):
+        raise ValueError("t_us and count must be [rows]")
+    sor = None
+    if stream_of_row is not None:
+        sor = np.ascontiguousarray(stream_of_row, np.int32)
+        if sor.shape != (rows,) or (rows and (sor.min() < 0 or sor.max() >= S)):
+            raise ValueError("stream_of_row must be [rows] with entries in [0, S)")
+    elif rows > S:
+        raise ValueError("more rows than streams")
+    prm = track_params(**params)
+    T = min(max(prm.max_tracks, 1), MAX_TRACKS)
+    o = {"tracks": np.zeros((rows, T), dt), "assigned": np.zeros((rows, Kp), np.int32),
+         "num_confirmed": np.zeros(rows, np.int32)}
+    stub = np.zeros(1, np.int64)  # rows = 0: an empty array's address may be NULL, and nothing is read
+
+    def ptr(a):
+        return (a if a.size else stub).ctypes.data_as(C.c_void_p)
+    out = TrackOutputs(*[ptr(o[n]) for n, _ in TrackOutputs._fields_])
+    check(load().tdoa_track_host(ptr(tracks), ptr(next_id), rows, None if sor is None else ptr(sor), ptr(t_us),
+                                 ptr(count), ptr(xy), Kp, C.byref(prm), C.byref(out)), "tdoa_track_host")
+    return o

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Config, Outputs, PeaksOutputs, PeaksParams, check, load
+from ._lib import Config, Outputs, PeaksOutputs, PeaksParams, TrackOutputs, check, load, track_params
 
 
 def _ptr(t: torch.Tensor | None):
@@ -348,6 +348,65 @@ class Localizer:
         check(load().tdoa_peaks(self._ctx, _ptr(scores), int(is_float), B, C.byref(prm),
                                 C.byref(s), C.c_void_p(st.cuda_stream)), "tdoa_peaks")
         return o
+
+    def track_batch(self, tracks: torch.Tensor, next_id: torch.Tensor, t_us: torch.Tensor, count: torch.Tensor,
+                    xy: torch.Tensor, stream_of_row: torch.Tensor | None = None, outputs=None, stream=None,
+                    **params) -> dict:
+        """One tracker update of caller-owned state from a block of measurements
+        (tdoa_track_batch, kernel k_track; the rule is in include/tdoa.h,
+        "Tracking").
+
+        tracks: uint8 [S][8][64] (tdoa_track records, all zero at start; view
+        its host copy with TRACK_DTYPE) and next_id: int32 [S], updated in
+        place.  Row i is stream stream_of_row[i] (int32 [rows]; None: stream
+        i) at time t_us[i] (int64, microseconds) with count[i] (int32)
+        measurements xy[i, :count[i]] (float32 [rows][Kp][2], metres, e.g. a
+        peaks() call's xy or xy_ls).  params: the tdoa_track_params fields
+        (_lib.TRACK_DEFAULTS).  outputs: a dict of tensors to write (tracks
+        uint8 [rows][T][64], assigned int32 [rows][Kp], num_confirmed int32
+        [rows]; a missing key is not written) -- fresh ones by default.
+        Asynchronous on `stream` (default: the current stream)."""
+        dev = self.torch_device
+        prm = track_params(**params)
+        S = tracks.shape[0] if tracks.dim() else 0
+        if tracks.dtype != torch.uint8 or tuple(tracks.shape) != (S, _lib.MAX_TRACKS, 64):
+            raise ValueError(f"tracks must be uint8 [S][{_lib.MAX_TRACKS}][64]")
+        if next_id.dtype != torch.int32 or tuple(next_id.shape) != (S,):
+            raise ValueError("next_id must be int32 [S]")
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[2] != 2:
+            raise ValueError("xy must be float32 [rows][Kp][2]")
+        rows, Kp = xy.shape[0], xy.shape[1]
+        if t_us.dtype != torch.int64 or tuple(t_us.shape) != (rows,):
+            raise ValueError("t_us must be int64 [rows]")
+        if count.dtype != torch.int32 or tuple(count.shape) != (rows,):
+            raise ValueError("count must be int32 [rows]")
+        if stream_of_row is None:
+            if rows > S:
+                raise ValueError("more rows than streams")
+        elif stream_of_row.dtype != torch.int32 or tuple(stream_of_row.shape) != (rows,):
+            raise ValueError("stream_of_row must be int32 [rows]")
+        T = min(max(prm.max_tracks, 1), _lib.MAX_TRACKS)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        if outputs is None:
+            with torch.cuda.stream(st):
+                outputs = {"tracks": torch.empty((rows, T, 64), dtype=torch.uint8, device=dev),
+                           "assigned": torch.empty((rows, Kp), dtype=torch.int32, device=dev),
+                           "num_confirmed": torch.empty(rows, dtype=torch.int32, device=dev)}
+        want = {"tracks": (torch.uint8, (rows, T, 64)), "assigned": (torch.int32, (rows, Kp)),
+                "num_confirmed": (torch.int32, (rows,))}
+        for name, t in outputs.items():
+            if name not in want or t.dtype != want[name][0] or tuple(t.shape) != want[name][1]:
+                raise ValueError(f"outputs[{name!r}] must be {want.get(name)}")
+        for t in (tracks, next_id, t_us, count, xy, stream_of_row, *outputs.values()):
+            if t is not None and (t.device != dev or not t.is_contiguous()):
+                raise ValueError(f"every tensor must be contiguous on {dev}")
+        if rows == 0:  # nothing to launch (and empty tensors have no address to pass)
+            return outputs
+        o = TrackOutputs(*[None if outputs.get(n) is None else outputs[n].data_ptr() for n, _ in TrackOutputs._fields_])
+        check(load().tdoa_track_batch(self.device, _ptr(tracks), _ptr(next_id), rows, _ptr(stream_of_row), _ptr(t_us),
+                                      _ptr(count), _ptr(xy), Kp, C.byref(prm), C.byref(o),
+                                      C.c_void_p(st.cuda_stream)), "tdoa_track_batch")
+        return outputs
 
     def cell_xy(self, cell: np.ndarray) -> np.ndarray:
         """((x - half_w)/scale, (half_h - y)/scale) of row-major cells, float32 as on device."""

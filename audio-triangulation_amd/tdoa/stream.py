@@ -26,6 +26,45 @@ up to `num_peaks` maxima of the EMA map of every frame the step listed
 refinement k_ls_stream); peaks_all() runs tdoa_peaks over the whole device
 state, est_ptr() hands that state out as a device address.
 
+track() / track_records() / tracks_all() follow sources across hops
+(tdoa_stream_track: k_track).  Per hop the order is step -> peaks -> track.
+Each stream owns a table of 8 track records (TRACK_DTYPE: id, status, hits,
+misses, x, y, vx, vy, p00, p01, p11, peak, t_us, upd_us), all zero at start,
+and a counter next_id, 0 at start (the first id is 1).  A listed slot is a row:
+its stream s, its time t = end * 1e6 / fs (int64 us, the EMA's clock), n = its
+peak count clamped to [0, Kp], measurements z_k = (zx, zy), k < n.  With
+T = max_tracks, r = meas_var, q = accel_psd, all float arithmetic fp32 with
+every operation rounded on its own and IEEE division, in exactly this order:
+  0. n <= 0: the row is not evaluated (state untouched: no miss is counted, no
+     time advances; the outputs are the unchanged table, assigned all 0).  A
+     measurement with a non-finite coordinate is invalid: neither associated
+     nor born.
+  1. coast-out: each live slot j < T, in slot order, with
+     t - upd_us > max_coast_us is zeroed (freed).
+  2. predict every live track: dt = (float)max(t - t_us, 0) / 1e6f;
+     x = x + vx*dt; y = y + vy*dt; a = dt*p11; c = (p01 + p01) + a; d = dt*c;
+     dt2 = dt*dt; dt3 = dt2*dt; p00 = (p00 + d) + (q*dt3)/3.0f;
+     p01 = (p01 + a) + (q*dt2)*0.5f; p11 = p11 + q*dt; t_us = t.
+  3. cost for live j, valid k: dx = zx - x; dy = zy - y; s = p00 + r;
+     c_jk = (dx*dx + dy*dy) / s; eligible iff c_jk <= gate_d2 (NaN: false).
+  4. greedy association: the eligible pair of minimum c_jk among tracks and
+     measurements both unassigned, ties to the lowest j, then the lowest k;
+     repeat until no eligible pair remains.
+  5. assigned track, from the old values: k0 = p00/s; k1 = p01/s;
+     x = x + k0*dx; y = y + k0*dy; vx = vx + k1*dx; vy = vy + k1*dy;
+     p11 = p11 - k1*p01; p01 = p01 - k0*p01; p00 = p00 - k0*p00; hits += 1;
+     misses = 0; upd_us = t; peak = k; status 1 with hits >= confirm_hits
+     becomes 2.
+  6. unassigned live track: misses += 1; peak = -1; freed when
+     misses >= max_misses.
+  7. births: each unassigned valid measurement, ascending k, takes the lowest
+     free slot < T (slots freed in 1 and 6 count) or is dropped:
+     id = ++next_id[s], status = confirm_hits <= 1 ? 2 : 1, hits = 1,
+     misses = 0, (x, y) = z, vx = vy = 0, p00 = r, p01 = 0,
+     p11 = init_vel_var, t_us = upd_us = t, peak = k.
+With gated_only=False peaks, a stream never updated reports cell 0 with L = 0
+and a track is born there: track gated peaks (the default) or use min_rel.
+
 mode="continuous" (a `gcc_phat` Localizer; tdoa_stream_create_continuous:
 k_stream_active in place of a trigger) chooses frames for continuous audio
 instead of clicks.  The ring is uint8 or int16 according to loc.sample_format.
@@ -44,8 +83,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (STREAM_TRIGGER_VAR_PCM16, PeaksOutputs, PeaksParams, StreamOutputs, StreamOutputsF, check,
-                   load)
+from ._lib import (MAX_TRACKS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS, PeaksOutputs, PeaksParams, StreamOutputs,
+                   StreamOutputsF, TrackOutputs, check, load, track_params)
 from .localizer import Localizer
 
 
@@ -129,6 +168,8 @@ class StreamPipeline:
         self._h = h
         self._peaks = {}  # (Kp, ls) -> the output tensors of peaks()
         self._peaks_last = None
+        self._tracks = {}  # (T, Kp) -> the output tensors of track()
+        self._tracks_last = None
 
     def step(self) -> dict:
         """One hop for every stream (asynchronous on self.stream)."""
@@ -195,6 +236,83 @@ class StreamPipeline:
         r["stream_id"] = self.out["stream_id"][:n].cpu().numpy()
         order = np.argsort(r["stream_id"], kind="stable")
         return {k: v[order] for k, v in r.items()}
+
+    def track(self, peaks: dict | None = None, use_ls: bool | None = None, **params) -> dict:
+        """One tracker update per listed stream from a peaks() result
+        (tdoa_stream_track, kernel k_track), asynchronous on self.stream: call
+        it after step() and peaks(), before the next step().
+
+        peaks: a dict with count [S] int32 and xy / xy_ls [S][Kp][2] float32 as
+        peaks() returns them (default: the last peaks() result; any tensors of
+        that layout do, the call does not depend on peaks()).  use_ls: take
+        xy_ls (None: when the result has it).  params: the tdoa_track_params
+        fields (_lib.TRACK_DEFAULTS).  Returns device tensors indexed by the
+        step's slots, rows < out["count"] written: tracks uint8 [S][T][64] (a
+        stream's slots 0..T-1 after the update; track_records() views them as
+        TRACK_DTYPE), assigned int32 [S][Kp] (the track id each peak went to or
+        was born as, 0 otherwise) and num_confirmed int32 [S].  They are
+        allocated once per (T, Kp) and reused by later calls."""
+        pk = self._peaks_last if peaks is None else peaks
+        if pk is None:
+            raise RuntimeError("track() reads the result of a peaks() call (or takes one as `peaks`)")
+        ls = ("xy_ls" in pk) if use_ls is None else bool(use_ls)
+        xy, count = pk["xy_ls" if ls else "xy"], pk["count"]
+        dev = self.loc.torch_device
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
+            raise ValueError("the measurements must be float32 [S][Kp][2]")
+        if count.dtype != torch.int32 or tuple(count.shape) != (self.S,):
+            raise ValueError("count must be int32 [S]")
+        if xy.device != dev or count.device != dev or not xy.is_contiguous() or not count.is_contiguous():
+            raise ValueError("count and the measurements must be contiguous on the localizer's device")
+        prm = track_params(**params)
+        Kp, T = xy.shape[1], min(max(prm.max_tracks, 1), MAX_TRACKS)
+        o = self._tracks.get((T, Kp))
+        if o is None:
+            S = self.S
+            o = {"tracks": torch.zeros((S, T, 64), dtype=torch.uint8, device=dev),
+                 "assigned": torch.zeros((S, max(Kp, 0)), dtype=torch.int32, device=dev),
+                 "num_confirmed": torch.zeros(S, dtype=torch.int32, device=dev)}
+            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+        s = TrackOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in TrackOutputs._fields_])
+        check(load().tdoa_stream_track(self._h, C.byref(prm), C.c_void_p(count.data_ptr()),
+                                       C.c_void_p(xy.data_ptr()) if xy.numel() else None, Kp, C.byref(s),
+                                       C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_track")
+        self._tracks[(T, Kp)] = o  # kept only once the library accepted the arguments
+        self._tracks_last = o
+        return o
+
+    def track_records(self) -> dict:
+        """Synchronously fetch the last track() call's rows of this step's slots,
+        sorted by stream, with the slots' stream_id attached; tracks is a
+        structured array [n][T] of TRACK_DTYPE."""
+        if self._tracks_last is None:
+            raise RuntimeError("track_records() reads the result of a track() call")
+        self.stream.synchronize()
+        n = int(self.out["count"].item())
+        r = {k: v[:n].cpu().numpy() for k, v in self._tracks_last.items()}
+        r["tracks"] = np.ascontiguousarray(r["tracks"]).view(np.dtype(TRACK_FIELDS))[..., 0]
+        r["stream_id"] = self.out["stream_id"][:n].cpu().numpy()
+        order = np.argsort(r["stream_id"], kind="stable")
+        return {k: v[order] for k, v in r.items()}
+
+    def tracks_all(self):
+        """Host snapshot of the whole track state, listed or not (synchronises):
+        (tracks [S][8] of TRACK_DTYPE, next_id [S] int32); all zero before the
+        first track() call (tdoa_stream_tracks_device)."""
+        tr, nid = C.c_void_p(), C.c_void_p()
+        check(load().tdoa_stream_tracks_device(self._h, C.byref(tr), C.byref(nid)), "tdoa_stream_tracks_device")
+        tracks = np.zeros((self.S, MAX_TRACKS), np.dtype(TRACK_FIELDS))
+        next_id = np.zeros(self.S, np.int32)
+        if tr.value:
+            self.stream.synchronize()
+            hip = load()  # the HIP runtime's symbols resolve through libtdoa.so, which is linked to it
+            hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+            for dst, src in ((tracks, tr.value), (next_id, nid.value)):
+                rc = hip.hipMemcpy(dst.ctypes.data_as(C.c_void_p), C.c_void_p(src), dst.nbytes, 2)  # device to host
+                if rc != 0:
+                    raise RuntimeError(f"copying the track state failed: hipError {rc}")
+        return tracks, next_id
 
     def est_ptr(self):
         """(device address, is_float) of the EMA state: int64 [S][P][K] (DIRECT)

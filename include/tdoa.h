@@ -533,6 +533,144 @@ int tdoa_stream_peaks(tdoa_stream *st, const tdoa_peaks_params *prm,
  * not only the listed ones; such calls follow the usual rule: stream-ordered
  * with the steps.  Host only; TDOA_ERR_INVALID for a NULL argument. */
 int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is_float);
+
+/* ---- Tracking: sources followed across hops from the per-hop peaks ----
+ * The rows tdoa_stream_peaks (or tdoa_peaks) reports are unlabelled and
+ * memoryless.  The tracker keeps, per stream, a table of TDOA_MAX_TRACKS
+ * records -- each a stable id, a position, a velocity and a covariance (a
+ * constant-velocity Kalman filter per axis, the two axes sharing one 2 x 2
+ * covariance) -- and updates it once per evaluated row from that row's
+ * measurements.  The reference has no such layer.
+ *
+ * State.  tracks[S][TDOA_MAX_TRACKS] tdoa_track records, all zero at start;
+ * next_id[S] int32, 0 at start: the first id given to a stream is 1.
+ *
+ * Inputs of a row: its stream s, its time t (int64 us), n = its count clamped
+ * to [0, Kp], and the measurements z_k = (zx, zy), k < n, of a float
+ * [rows][Kp][2] block.  With T = max_tracks, r = meas_var, q = accel_psd:
+ *
+ * Per evaluated row.  All float arithmetic is fp32, every operation rounded on
+ * its own (no fused multiply-add, no reassociation), division IEEE; the steps
+ * run in exactly this order:
+ *   0. A row with n <= 0 is not evaluated: the state is untouched (no miss is
+ *      counted, no time advances), the row's outputs are the unchanged table
+ *      and assigned is all 0.  A measurement with a non-finite coordinate is
+ *      invalid: it is neither associated nor born.
+ *   1. Coast-out.  Each live slot j < T, in slot order: if
+ *      t - upd_us > max_coast_us the record is zeroed (freed).
+ *   2. Predict every live track:
+ *        dt  = (float)max(t - t_us, 0) / 1e6f
+ *        x   = x + vx*dt;   y = y + vy*dt
+ *        a   = dt*p11;      c = (p01 + p01) + a;   d = dt*c
+ *        dt2 = dt*dt;       dt3 = dt2*dt
+ *        p00 = (p00 + d) + (q*dt3)/3.0f
+ *        p01 = (p01 + a) + (q*dt2)*0.5f
+ *        p11 = p11 + q*dt
+ *        t_us = t
+ *   3. Cost, for live j and valid k:
+ *        dx = zx - x;  dy = zy - y;  s = p00 + r;  c_jk = (dx*dx + dy*dy) / s
+ *      the pair is eligible iff c_jk <= gate_d2 (a NaN compares false).
+ *   4. Greedy association.  Repeatedly take the eligible pair of minimum c_jk
+ *      among tracks and measurements both still unassigned, ties to the lowest
+ *      j, then the lowest k; assign it; stop when no eligible pair remains.
+ *   5. Assigned track, all from the old values:
+ *        k0 = p00/s;  k1 = p01/s
+ *        x = x + k0*dx;    y = y + k0*dy
+ *        vx = vx + k1*dx;  vy = vy + k1*dy
+ *        p11 = p11 - k1*p01;  p01 = p01 - k0*p01;  p00 = p00 - k0*p00
+ *        hits += 1;  misses = 0;  upd_us = t;  peak = k
+ *        if status == 1 && hits >= confirm_hits then status = 2
+ *   6. Unassigned live track: misses += 1; peak = -1; if
+ *      misses >= max_misses the record is zeroed (freed).
+ *   7. Births.  Each unassigned valid measurement, in ascending k, takes the
+ *      lowest free slot < T (slots freed in steps 1 and 6 count as free); with
+ *      no free slot it is dropped.  The new track: id = ++next_id[s],
+ *      status = confirm_hits <= 1 ? 2 : 1, hits = 1, misses = 0, (x, y) = z,
+ *      vx = vy = 0, p00 = r, p01 = 0, p11 = init_vel_var, t_us = upd_us = t,
+ *      peak = k.
+ *
+ * Outputs (tdoa_track_outputs; each optional, at least one set):
+ *   tracks [rows][T]       a copy of the stream's slots 0..T-1 after the row;
+ *   assigned [rows][Kp]    the id of the track measurement k was assigned to or
+ *                          born as, 0 otherwise (dropped, invalid, k >= n);
+ *   num_confirmed [rows]   the slots < T with status 2 after the row.
+ * Slots >= T of the state are neither read nor written.  Two rows of one call
+ * naming the same stream is undefined; the pipeline's lists never do. */
+#define TDOA_MAX_TRACKS 8
+
+typedef struct tdoa_track {          /* 64 bytes, 8-byte aligned */
+    int32_t id;       /* >= 1; 0 = free slot (then every field is 0) */
+    int32_t status;   /* 0 free, 1 tentative, 2 confirmed */
+    int32_t hits;     /* measurements assigned since birth (birth counts 1) */
+    int32_t misses;   /* consecutive evaluations without one */
+    float   x, y, vx, vy;      /* metres, metres/s, grid frame (as xy / xy_ls) */
+    float   p00, p01, p11;     /* per-axis covariance: pos, pos-vel, vel (shared by x and y) */
+    int32_t peak;     /* peak index assigned at the last evaluation, -1 none */
+    int64_t t_us;     /* time the state is predicted to */
+    int64_t upd_us;   /* time of the last assigned measurement */
+} tdoa_track;
+
+typedef struct tdoa_track_params {
+    int32_t max_tracks;    /* T, 1..TDOA_MAX_TRACKS: slots 0..T-1 are used */
+    int32_t confirm_hits;  /* >= 1: tentative -> confirmed when hits >= this */
+    int32_t max_misses;    /* >= 1: freed when misses reaches this */
+    int64_t max_coast_us;  /* > 0: freed when t - upd_us exceeds this */
+    float   gate_d2;       /* > 0: association gate on the normalised distance^2 */
+    float   meas_var;      /* r  > 0, m^2 */
+    float   accel_psd;     /* q >= 0, m^2/s^3 */
+    float   init_vel_var;  /* > 0, m^2/s^2 */
+} tdoa_track_params;
+
+typedef struct tdoa_track_outputs {  /* any may be NULL, not all */
+    tdoa_track *tracks;      /* [rows][T] */
+    int32_t *assigned;       /* [rows][Kp] */
+    int32_t *num_confirmed;  /* [rows] */
+} tdoa_track_outputs;
+
+/* The block form, as tdoa_peaks is to tdoa_stream_peaks: rows of caller-owned
+ * device state (tracks [S][TDOA_MAX_TRACKS], next_id [S]) updated from device
+ * blocks; row i is stream stream_of_row[i] (device [rows]; NULL: stream i).
+ * Asynchronous on `stream`, no allocation, no synchronisation; kernel k_track,
+ * one wave per row.  rows = 0 returns TDOA_OK without a launch.
+ * TDOA_ERR_INVALID, with tdoa_last_error naming the cause, before any device
+ * call (nothing is launched, no output is touched): a NULL prm, out, count,
+ * xy, t_us or state pointer; all outputs NULL; Kp outside 1..TDOA_MAX_PEAKS;
+ * a parameter outside its range above or non-finite; rows < 0 or
+ * rows >= 2^31. */
+int tdoa_track_batch(int device, tdoa_track *tracks, int32_t *next_id, int64_t rows,
+                     const int32_t *stream_of_row /* NULL: row i is stream i */,
+                     const int64_t *t_us /* [rows] */, const int32_t *count,
+                     const float *xy /* [rows][Kp][2] */, int32_t Kp,
+                     const tdoa_track_params *prm, const tdoa_track_outputs *out, void *stream);
+/* The same rule on the host, from the same inline predict / cost / update
+ * functions: every pointer is a host pointer, rows are evaluated in order. */
+int tdoa_track_host(tdoa_track *tracks, int32_t *next_id, int64_t rows,
+                    const int32_t *stream_of_row, const int64_t *t_us, const int32_t *count,
+                    const float *xy, int32_t Kp, const tdoa_track_params *prm,
+                    const tdoa_track_outputs *out);
+/* The streaming form.  The rows are the slots of the step enqueued last on st
+ * (tdoa_stream_peaks' contract: the pipeline's own list, its counter slot
+ * clamped to [0, S] on the device; nothing is launched if there has been no
+ * step since create / reset); count (device [S]) and xy (device [S][Kp][2]) are
+ * a tdoa_stream_peaks call's count and xy or xy_ls, indexed by slot; a row's
+ * time is the EMA's own clock t = (uint64)end[slot] * 1000000 / fs, read from
+ * the pipeline's list on the device.  Outputs are indexed by slot; rows past
+ * the step's count are not written.  Per call order: step, peaks, track.
+ * The state, S * (8 * 64 + 4) bytes owned by st, is allocated and zeroed at
+ * the first call and never again; tdoa_stream_reset zeroes it.  Asynchronous
+ * on `stream`, never synchronises the host, a plain launch whether or not the
+ * pipeline replays graphs; it must be stream-ordered after the peaks call and
+ * before the pipeline's next step.  TDOA_ERR_INVALID as above (st in place of
+ * the state pointers). */
+int tdoa_stream_track(tdoa_stream *st, const tdoa_track_params *prm,
+                      const int32_t *count /* device [S] */,
+                      const float *xy /* device [S][Kp][2] */, int32_t Kp,
+                      const tdoa_track_outputs *out, void *stream);
+/* The pipeline's track state as device pointers (tracks [S][TDOA_MAX_TRACKS],
+ * next_id [S]) for every stream, listed or not; both NULL before the first
+ * tdoa_stream_track.  Valid until tdoa_stream_destroy.  Host only;
+ * TDOA_ERR_INVALID for a NULL argument. */
+int tdoa_stream_tracks_device(tdoa_stream *st, const tdoa_track **tracks, const int32_t **next_id);
 int tdoa_stream_destroy(tdoa_stream *st);
 
 const char *tdoa_last_error(void);

@@ -1,9 +1,16 @@
 // tdoa_frame16_frames.inc -- the body of the per-frame long-frame kernels of
 // tdoa_phat_r16.hip, included once per kernel: k_frame16<C, M, DM, XS, FG>
-// (8-bit ADC front end) and k_f16_pcm16<C, M, DM> (TDOA_SAMPLES_PCM16).  It
+// (8-bit ADC front end), k_f16_pcm16<C, M, DM> (TDOA_SAMPLES_PCM16) and
+// k_f16_ring<C, M, PCM16, BW> (a streaming step's listed frames).  It
 // reads the kernel's parameters (kp, out, frames, B, e2) and the constants C,
-// M, DM, XS, FG and PCM16 of the including scope; the two formats differ in
-// frame16_forward's front-end block alone.  Text rather than a __device__
+// M, DM, XS, FG, PCM16, RING and BW of the including scope; the two formats
+// differ in frame16_forward's front-end block alone.  RING (k_f16_ring only):
+// B is the step's clamped frame count, frame fr is the step's slot fr, staged
+// by `fetch` from its stream's capture ring (rs: f16_ring_src) instead of
+// `frames`, and every output is indexed by slot; BW (RING only): the pairs'
+// cross spectra are multiplied by the weight table kp.bin_w, bin b by w[b] and
+// bin C - b by w[C - b] (b = 0 pairs with bin C, the self-paired bin takes
+// w[C / 2]: tdoa_stream_phat_hop.inc's mapping).  Text rather than a __device__
 // function: inlined from one, every k_frame16 instantiation's code came out
 // different (the callee is simplified on its own, without the kernel's
 // work-group size, before it is inlined).
@@ -13,6 +20,8 @@
     constexpr int WPG = T / 64;  // waves per group (4 or 2)
     static_assert(WPG == 2 || WPG == 4, "group of 2 or 4 waves");
     static_assert(DM == 0 || DM == 1, "deferred-output mode");
+    static_assert(RING || !BW, "the batch kernels take no weight table (a weighted batch runs the two-pass route)");
+    static_assert(!RING || !FG, "no fused grid over a ring");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f2 *bufs = (f2 *)smem;                    // [G][BUF]
     f2 *xhalf = bufs + G * BUF;               // [G] U_m[C / 2]
@@ -21,8 +30,13 @@
     f2 *ttl = (f2 *)(lagl + TDOA_MAX_PAIRS);  // [3][16][16] the r16 twiddle tables
     float *priorl = (float *)(ttl + 3 * 16 * 16);  // [128] the lag prior (K <= 127)
     f2 *tw3 = (f2 *)(priorl + 128);  // [R1][64] pass-3 twiddles per lane (row 0 unused)
-    uint32_t *winl = (uint32_t *)(tw3 + R1 * 64);  // f16_win_lds: [C / 2] window words
-    float *scl = (float *)(winl + (f16_win_lds<C>() ? C / 2 : 0));  // DM 1: [P][K] raw scores of the frame
+    // BW: the weights take registers through the pair rounds, where a byte
+    // ring's sixteen loads are in flight; the window words leave theirs for LDS
+    // (free next to the deferred scores at both ring shapes)
+    constexpr bool WINL = f16_win_lds<C>() || BW;
+    constexpr int WMODE = BW ? 1 : f16_win_mode<C>();
+    uint32_t *winl = (uint32_t *)(tw3 + R1 * 64);  // WINL: [C / 2] window words
+    float *scl = (float *)(winl + (WINL ? C / 2 : 0));  // DM 1: [P][K] raw scores of the frame
     // FG: the fused grid's LDS (FgLds) after scl, 16-B aligned; its levels in
     // the last round's idle groups' buffers
     constexpr int GI0 = P - (ROUNDS - 1) * G;  // first idle group of the last round
@@ -69,13 +83,13 @@
     f2 twh = tw2[C / 2];
 #endif
     uint32_t wr[8] = {};  // f16_win_mode 2: this thread's window words
-    if constexpr (f16_win_mode<C>() == 2) {
+    if constexpr (WMODE == 2) {
         const int j0 = (int)threadIdx.x - g * T;
 #pragma unroll
         for (int s2 = 0; s2 < 8; s2++)
             wr[s2] = win[j0 + T * s2];
     }
-    if constexpr (f16_win_lds<C>()) {
+    if constexpr (WINL) {
         for (int i = threadIdx.x; i < C / 2; i += 1024)
             winl[i] = win[i];
         __syncthreads();  // the forward reads the window before its first barrier
@@ -207,12 +221,50 @@
     // them instead of opening every frame
     uint32_t w[8];
     auto fetch = [&](int64_t f) {
+        if constexpr (RING) {
+            // slot f's frame from its stream's ring: word q = j + T s holds
+            // samples 2q, 2q + 1 of mic mg, ring elements ((at + n) mod cl) M + mg
+            // (bytes widened as the batch frames are, or the int16 samples);
+            // element loads: a ring needs no alignment beyond its sample's,
+            // and a frame (C <= cl samples from at < cl) wraps at most once
+            // One stream's ring is under 2^31 bytes (tdoa_f16_ring_shape's
+            // caller checks it): the stream's and the mic's base is scalar and
+            // a sample's byte offset one 32-bit register, dead once its load is
+            // issued (64-bit indices per sample spilled)
+            using T_ = typename std::conditional<PCM16, uint16_t, uint8_t>::type;
+            typedef unsigned short v2us_ __attribute__((ext_vector_type(2)));
+            constexpr uint32_t ST = M * sizeof(T_);  // bytes from a sample to the mic's next
+            const int64_t cl = rs.capture_len;
+            int sid = __builtin_amdgcn_readfirstlane(rs.ids[f]);
+            sid = sid < 0 ? 0 : (sid >= rs.nstreams ? rs.nstreams - 1 : sid);
+            const int64_t at64 = rs.ring_at[f];
+            const uint32_t cl32 = (uint32_t)cl;
+            uint32_t at = (uint32_t)__builtin_amdgcn_readfirstlane((int)(at64 < 0 ? 0 : (at64 >= cl ? cl - 1 : at64)));
+            const char *cap = reinterpret_cast<const char *>(rs.capture) +
+                              ((size_t)sid * (size_t)cl * M + (size_t)__builtin_amdgcn_readfirstlane(mg)) * sizeof(T_);
+            const uint32_t j0 = (uint32_t)((int)threadIdx.x - g * T);
+#pragma unroll
+            for (int s = 0; s < 8; s++) {
+                uint32_t n0 = at + 2 * (j0 + T * s);
+                n0 = n0 >= cl32 ? n0 - cl32 : n0;
+                const uint32_t n1 = n0 + 1 >= cl32 ? 0 : n0 + 1;
+                v2us_ x;
+                x.x = *reinterpret_cast<const T_ *>(cap + n0 * ST);
+                x.y = *reinterpret_cast<const T_ *>(cap + n1 * ST);
+                w[s] = __builtin_bit_cast(uint32_t, x);
+            }
+        } else {
         const uint32_t *x = reinterpret_cast<const uint32_t *>(frames + (f * M + mg) * (int64_t)C) +
                             ((int)threadIdx.x - g * T);
 #pragma unroll
         for (int s = 0; s < 8; s++)
             w[s] = __builtin_nontemporal_load(x + T * s);
+        }
     };
+    if constexpr (RING) {
+        if ((int64_t)blockIdx.x >= B)
+            return;  // no listed slot for this workgroup: no ring read
+    }
     fetch(blockIdx.x);
     // the next frame's words are waited for here, before this wave's output
     // stores: gfx9's vmcnt counts stores and retires in order, and with stores
@@ -269,13 +321,13 @@
             if (prev >= 0)
                 epi16(prev, ps);  // the previous frame's outputs (scl holds its scores until round 0's pass 3)
         };
-        frame16_forward<C, f16_win_mode<C>(), decltype(fwd_mark), XS, decltype(lag_hook), decltype(fwd_pre), PCM16>(
-            w, f16_win_lds<C>() ? winl : win, wr, buf, red, tt, tid, g, j, pj, kp.log2N, fwd_mark, lag_hook, fwd_pre);
+        frame16_forward<C, WMODE, decltype(fwd_mark), XS, decltype(lag_hook), decltype(fwd_pre), PCM16>(
+            w, WINL ? winl : win, wr, buf, red, tt, tid, g, j, pj, kp.log2N, fwd_mark, lag_hook, fwd_pre);
         if (prev >= 0)
             gate_of(prev);  // its lags are in lagl since the forward's closing barrier
     } else {
-        frame16_forward<C, f16_win_mode<C>(), decltype(fwd_mark), XS, NoHook16, decltype(fwd_pre), PCM16>(
-            w, f16_win_lds<C>() ? winl : win, wr, buf, red, tt, tid, g, j, pj, kp.log2N, fwd_mark, NoHook16(), fwd_pre);
+        frame16_forward<C, WMODE, decltype(fwd_mark), XS, NoHook16, decltype(fwd_pre), PCM16>(
+            w, WINL ? winl : win, wr, buf, red, tt, tid, g, j, pj, kp.log2N, fwd_mark, NoHook16(), fwd_pre);
     }
     if (fr == diag_fr)
         F16_MARK();  // forward transforms done
@@ -326,6 +378,22 @@
 #endif
     if (fr == diag_fr)
         F16_MARK();  // unit spectra in registers
+    // BW: the weights of this thread's bins b = tid + 1024 s and C - b, and
+    // w[C / 2], requested per frame ahead of the next frame's words (they
+    // return first).  LDS is full at 8 x 2048, and registers held for the
+    // launch spilled in the forward, where the lagged epilogue runs
+    float bwk[NS] = {}, bwn[NS] = {}, bwh = 0.0f;
+    if constexpr (BW) {
+        // (the table's address through the opaque kernarg pointer: read here,
+        // not held in scalar registers across the frame loop)
+        const float *bwt = kernarg_kp()->bin_w;
+#pragma unroll
+        for (int s = 0; s < NS; s++) {
+            bwk[s] = bwt[tid + 1024 * s];
+            bwn[s] = bwt[C - (tid + 1024 * s)];
+        }
+        bwh = bwt[C / 2];
+    }
     {
         const int64_t fn = fr + gridDim.x;
         fetch(fn < B ? fn : fr);  // the next frame's words (or a harmless re-read)
@@ -357,15 +425,21 @@
                 f2 *yb = bufs + decltype(gc)::value * BUF;
 #pragma unroll
                 for (int s = 0; s < NS; s++) {
-                    const f2 Rk = c_conjmul(Ub[pi][s], Ub[pj][s]);  // R[b]
-                    const f2 Rq = c_conjmul(Un[pi][s], Un[pj][s]);  // R[C-b]
+                    f2 Rk = c_conjmul(Ub[pi][s], Ub[pj][s]);  // R[b]
+                    f2 Rq = c_conjmul(Un[pi][s], Un[pj][s]);  // R[C-b]
+                    if constexpr (BW) {
+                        Rk = bwk[s] * Rk;
+                        Rq = bwn[s] * Rq;
+                    }
                     const f2 ss = c_addconj(Rk, Rq);
                     const f2 qq = c_mulconj(c_subconj(Rk, Rq), twb[s]);
                     yb[yb0[s]] = c_add_i(ss, qq);
                     yb[yb1[s]] = c_conj_add_mi(ss, qq);
                 }
                 if (!F16_YHALF && tl == 0) {  // Y[C/2] from R[C/2] alone
-                    const f2 Rh = c_conjmul(xhalf[pi], xhalf[pj]);
+                    f2 Rh = c_conjmul(xhalf[pi], xhalf[pj]);
+                    if constexpr (BW)
+                        Rh = bwh * Rh;
                     yb[lidx<XS>(C / 2)] = c_add_i(c_addconj(Rh, Rh), c_mulconj(c_subconj(Rh, Rh), twh));
                 }
             }
@@ -384,7 +458,9 @@
                 q -= M - 1 - pi;
                 pi++;
             }
-            const f2 Rh = c_conjmul(xhalf[pi], xhalf[pi + 1 + q]);
+            f2 Rh = c_conjmul(xhalf[pi], xhalf[pi + 1 + q]);
+            if constexpr (BW)
+                Rh = bwh * Rh;
             bufs[tl * BUF + lidx<XS>(C / 2)] = c_add_i(c_addconj(Rh, Rh), c_mulconj(c_subconj(Rh, Rh), twh));
         }
 #endif

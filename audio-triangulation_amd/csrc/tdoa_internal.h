@@ -215,6 +215,22 @@ int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16
 int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
                             float *est, float *max_Lf, int64_t S, float phat_eps, int grid, void *stream,
                             bool pcm16 = false);
+// the GCC_PHAT hop of the long-frame shapes k_stream_phat's LDS cannot hold
+// (8 mics x 2048, 4 x 4096): k_f16_ring (tdoa_phat_r16.hip: k_frame16's body
+// over the step's listed frames, staged from the capture rings; kp.bin_w picks
+// the weighted instantiation) writes by slot lags [S][P], gate [S] and the
+// weighted scores [S][P][K], and k_stream_ema_grid (tdoa_stream_phat.hip) runs
+// record, EMA and grid scan on them and the step's bookkeeping.  A stream's
+// ring must stay under 2^31 bytes (32-bit sample offsets in the kernel).
+bool tdoa_f16_ring_shape(const tdoa_kparams &kp);
+// (its launch size for S streams, capped by `cap` > 0; 0: no workgroup fits)
+int tdoa_f16_ring_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16);
+int tdoa_launch_f16_ring(const tdoa_stream_params &sp, const tdoa_kparams &kp, int32_t *lags, uint8_t *gate,
+                         float *weighted, int64_t S, float phat_eps, int grid, void *stream, bool pcm16);
+int tdoa_stream_ema_grid_size(const tdoa_kparams &kp, int64_t S, int cap);
+int tdoa_launch_stream_ema_grid(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
+                                float *est, float *max_Lf, const float *weighted, const int32_t *lags,
+                                const uint8_t *gate, int64_t S, int grid, void *stream);
 int tdoa_launch_average(const tdoa_kparams &kp, int64_t S, int64_t *est,
                         const int64_t *fresh, const float *decay, int32_t *best,
                         const tdoa_kout *solve, void *stream);

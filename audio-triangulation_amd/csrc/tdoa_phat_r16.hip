@@ -221,6 +221,16 @@ struct ColIdx {
     }
 };
 
+// k_f16_ring's frame source: the list a streaming step's selector wrote
+// (tdoa_stream_params) and the capture rings it points into
+struct f16_ring_src {
+    const uint8_t *capture;  // [S][capture_len][M] uint8, or int16 samples (PCM16)
+    int64_t capture_len;
+    const int32_t *ids;      // [S] slot -> stream
+    const int64_t *ring_at;  // [S] ring index of the slot's first frame sample
+    int32_t nstreams;
+};
+
 template <int R>
 __device__ constexpr int brev(int k)
 {
@@ -1349,7 +1359,8 @@ __global__ void __launch_bounds__(1024, 1) k_frame16(tdoa_kparams kp, tdoa_kout 
                                                      const int16_t *__restrict__ frames, int64_t B,
                                                      float e2)
 {
-    constexpr bool PCM16 = false;
+    constexpr bool PCM16 = false, RING = false, BW = false;
+    constexpr f16_ring_src rs{};  // (RING only)
 #include "tdoa_frame16_frames.inc"
 }
 // full-range int16 frames (TDOA_SAMPLES_PCM16): k_frame16's body for its four
@@ -1359,7 +1370,27 @@ __global__ void __launch_bounds__(1024, 1) k_f16_pcm16(tdoa_kparams kp, tdoa_kou
                                                        const int16_t *__restrict__ frames, int64_t B,
                                                        float e2)
 {
-    constexpr bool XS = F16_XS != 0, FG = false, PCM16 = true;
+    constexpr bool XS = F16_XS != 0, FG = false, PCM16 = true, RING = false, BW = false;
+    constexpr f16_ring_src rs{};  // (RING only)
+#include "tdoa_frame16_frames.inc"
+}
+// the long-frame kernel over a streaming step's listed frames (tdoa_stream.cpp:
+// the shapes k_stream_phat's LDS cannot hold): k_frame16's body with the deferred
+// outputs, persistent over the slots 0 .. *count - 1 (clamped to [0, nstreams]).
+// Slot i's frame is staged from the capture ring of stream rs.ids[i] at
+// rs.ring_at[i] (uint8 elements, or int16 with PCM16); out.lags [S][P], out.gate
+// [S] and out.weighted_f [S][P][K] are indexed by slot.  BW: kp.bin_w is in
+// force.  (kp, out) stay the first two parameters (kernarg_out)
+template <int C, int M, bool PCM16, bool BW>
+__global__ void __launch_bounds__(1024, 1) k_f16_ring(tdoa_kparams kp, tdoa_kout out, f16_ring_src rs,
+                                                      const int32_t *__restrict__ count, float e2)
+{
+    constexpr bool XS = F16_XS != 0, FG = false, RING = true;
+    constexpr int DM = 1;
+    constexpr const int16_t *frames = nullptr;  // (batch only)
+    // read once; at most one slot per stream: a corrupted counter cannot index past [S]
+    const int cnt_raw = *count;
+    const int64_t B = cnt_raw < 0 ? 0 : (cnt_raw > rs.nstreams ? rs.nstreams : cnt_raw);
 #include "tdoa_frame16_frames.inc"
 }
 #undef F16_MARK
@@ -1491,6 +1522,55 @@ int launch_frame16(const tdoa_kparams &kp, const tdoa_kout &out, const int16_t *
     return 0;
 }
 
+
+// k_f16_ring's dynamic LDS: the deferred outputs' as launch_frame16 sizes it;
+// BW keeps the window words in LDS too (where the batch layout has none)
+template <int C, int M>
+size_t f16_ring_lds(const tdoa_kparams &kp, bool bw)
+{
+    return frame16_lds_base<C>() + (size_t)(M * (M - 1) / 2) * kp.K * sizeof(float) +
+           (bw && !f16_win_lds<C>() ? (size_t)C * 2 : 0);
+}
+// its launch size for S streams: the workgroups resident with either weight
+// form (one per CU), never more than S or than `cap` (> 0); 0: none fits
+template <int C, int M>
+int f16_ring_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16)
+{
+    int64_t grid = S;
+    for (int bw = 0; bw < 2; bw++) {
+        const void *fn = pcm16 ? (bw ? (const void *)k_f16_ring<C, M, true, true> : (const void *)k_f16_ring<C, M, true, false>)
+                               : (bw ? (const void *)k_f16_ring<C, M, false, true> : (const void *)k_f16_ring<C, M, false, false>);
+        const size_t lds = f16_ring_lds<C, M>(kp, bw != 0);
+        const int res = lds <= 160 * 1024 ? tdoa_resident_blocks(fn, 1024, lds) : 0;
+        if (res < 1)
+            return 0;
+        grid = grid < res ? grid : res;
+    }
+    if (cap > 0 && grid > cap)
+        grid = cap;
+    return (int)(grid > 0 ? grid : 1);
+}
+template <int C, int M>
+int launch_f16_ring(const tdoa_kparams &kp, const tdoa_kout &out, const f16_ring_src &rs, const int32_t *count,
+                    float e2, int grid, bool pcm16, hipStream_t st)
+{
+    const bool bw = kp.bin_w != nullptr;
+    const size_t lds = f16_ring_lds<C, M>(kp, bw);
+    const dim3 gd((unsigned)(grid > 0 ? grid : 1)), bd(1024);
+    if (pcm16) {
+        if (bw)
+            hipLaunchKernelGGL((k_f16_ring<C, M, true, true>), gd, bd, lds, st, kp, out, rs, count, e2);
+        else
+            hipLaunchKernelGGL((k_f16_ring<C, M, true, false>), gd, bd, lds, st, kp, out, rs, count, e2);
+    } else {
+        if (bw)
+            hipLaunchKernelGGL((k_f16_ring<C, M, false, true>), gd, bd, lds, st, kp, out, rs, count, e2);
+        else
+            hipLaunchKernelGGL((k_f16_ring<C, M, false, false>), gd, bd, lds, st, kp, out, rs, count, e2);
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_f16_ring launch");
+}
 
 #if TDOA_AB  // the A/B kernel k_frame16w: built into tools libraries only (Makefile "ab")
 // ------------------------------------------------ fused, one wave per pair
@@ -2016,6 +2096,38 @@ int tdoa_launch_phat_r16(const tdoa_kparams &kp, const tdoa_kout &out, const int
         return launch_frame16<2048, 4>(kp, out, frames, B, e2, st);
     return kp.N == 4096 ? launch_r16<4096>(kp, out, frames, B, e2, scratch, scratch_bytes, st)
                         : launch_r16<2048>(kp, out, frames, B, e2, scratch, scratch_bytes, st);
+}
+
+// the streaming long-frame route (k_f16_ring): the shapes it is built for
+bool tdoa_f16_ring_shape(const tdoa_kparams &kp)
+{
+    return tdoa_phat_r16_fits(kp.M, kp.N, kp.S) && kp.K <= 127 && kp.P == kp.M * (kp.M - 1) / 2 &&
+           ((kp.N == 2048 && kp.M == 8) || (kp.N == 4096 && kp.M == 4));
+}
+
+int tdoa_f16_ring_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16)
+{
+    if (!tdoa_f16_ring_shape(kp))
+        return 0;
+    return kp.N == 2048 ? f16_ring_grid<2048, 8>(kp, S, cap, pcm16) : f16_ring_grid<4096, 4>(kp, S, cap, pcm16);
+}
+
+int tdoa_launch_f16_ring(const tdoa_stream_params &sp, const tdoa_kparams &kp, int32_t *lags, uint8_t *gate,
+                         float *weighted, int64_t S, float phat_eps, int grid, void *stream, bool pcm16)
+{
+    if (!tdoa_f16_ring_shape(kp))
+        return tdoa_set_error(-1, "k_f16_ring: unsupported shape");
+    float e2 = phat_eps * 4294967296.0f;  // tdoa_launch_phat_r16's floor
+    if (!(e2 >= 1e-30f))
+        e2 = 1e-30f;
+    tdoa_kout out{};
+    out.lags = lags;
+    out.gate = gate;
+    out.weighted_f = weighted;
+    const f16_ring_src rs{sp.capture, sp.capture_len, sp.ids, sp.ring_at, (int32_t)S};
+    if (kp.N == 2048)
+        return launch_f16_ring<2048, 8>(kp, out, rs, sp.count, e2, grid, pcm16, (hipStream_t)stream);
+    return launch_f16_ring<4096, 4>(kp, out, rs, sp.count, e2, grid, pcm16, (hipStream_t)stream);
 }
 
 #ifdef TDOA_DIAG

@@ -11,7 +11,11 @@
 // (device-sized batch, EMA + grid on the EMA scores fused) -- or, for shapes
 // that kernel does not solve, k_direct -> k_stream_update; of a GCC_PHAT
 // pipeline k_stream_phat (tdoa_stream_phat.hip: float scores, float EMA state,
-// max_Lf), k_stream_phat_pcm16 on an int16 ring (tdoa_stream_create_pcm16).
+// max_Lf), k_stream_phat_pcm16 on an int16 ring (tdoa_stream_create_pcm16) --
+// or, for the long-frame shapes its LDS cannot hold (8 mics x 2048, 4 x 4096),
+//   selector -> k_f16_ring -> k_stream_ema_grid
+// (tdoa_phat_r16.hip: the batch engine's long-frame kernel over the listed
+// frames; then the EMA and grid half of k_stream_phat on its scores).
 // The hop's frame counter alternates between two slots by hop parity: the
 // selector zeroes the other slot for the next hop (a memset node cost 3.9 us
 // per hop), so the two parities are two captured graphs.
@@ -70,7 +74,14 @@ struct tdoa_stream {
     bool phat = false;      // GCC_PHAT pipeline: k_stream_phat after the selector
     float *est_f = nullptr; // ... its EMA state [S][P][K] (sp.est is null)
     float phat_eps = 0.0f;
-    int phat_grid = 1;      // k_stream_phat's launch size
+    int phat_grid = 1;      // k_stream_phat's launch size (f16: k_stream_ema_grid's)
+    // the long-frame route (k_f16_ring -> k_stream_ema_grid) and its per-slot
+    // scratch, carved from mem: weighted scores [S][P][K], lags [S][P], gate [S]
+    bool f16 = false;
+    int f16_grid = 1;       // k_f16_ring's launch size
+    float *f16_w = nullptr;
+    int32_t *f16_lags = nullptr;
+    uint8_t *f16_gate = nullptr;
     bool pcm16 = false;     // int16 capture ring (tdoa_stream_create_pcm16): k_stream_trigger_lds<int16_t>,
                             // k_stream_phat_pcm16; the format is the pipeline's from creation on
     bool continuous = false;  // tdoa_stream_create_continuous: k_stream_active lists the frames, no trigger
@@ -113,6 +124,16 @@ int enqueue_step(tdoa_stream *st, const step_out &out, hipStream_t s, int par)
         kp.bin_w = ck->bin_w;
         kp.bin_lo = ck->bin_lo;
         kp.bin_hi = ck->bin_hi;
+        if (st->f16) {
+            const tdoa_stream_kout ko = to_kout(out);
+            int32_t *lags = ko.lags ? ko.lags : st->f16_lags;
+            rc = tdoa_launch_f16_ring(sp, kp, lags, st->f16_gate, st->f16_w, st->S, st->phat_eps, st->f16_grid, s,
+                                      st->pcm16);
+            if (rc)
+                return rc;
+            return tdoa_launch_stream_ema_grid(sp, kp, ko, st->est_f, out.max_Lf, st->f16_w, lags, st->f16_gate,
+                                               st->S, st->phat_grid, s);
+        }
         return tdoa_launch_stream_phat(sp, kp, to_kout(out), st->est_f, out.max_Lf, st->S, st->phat_eps,
                                        st->phat_grid, s, st->pcm16);
     }
@@ -189,7 +210,12 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
         return tdoa_fail(TDOA_ERR_INVALID, "%s: this capture ring is 8-bit and the context's sample format is PCM16 "
                                            "(tdoa_set_sample_format): tdoa_stream_create_pcm16 takes int16 rings", fn);
     }
-    if (phat && !tdoa_stream_phat_fits(kp))
+    // the long-frame route: the two shapes k_stream_phat's LDS cannot hold
+    const bool f16 = phat && tdoa_f16_ring_shape(kp) && !tdoa_stream_phat_fits(kp);
+    if (f16 && capture_len > (((int64_t)1 << 31) - 1) / (M * (pcm16 ? 2 : 1)))
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: capture_len %lld: a stream's ring of %d mics x frame_len %d must stay "
+                                           "under 2^31 bytes", fn, (long long)capture_len, M, N);
+    if (phat && !f16 && !tdoa_stream_phat_fits(kp))
         return tdoa_fail(TDOA_ERR_INVALID,
                          "%s: GCC_PHAT with %d mics x frame_len %d needs %zu bytes of LDS per "
                          "workgroup (limit 160 KiB)",
@@ -214,13 +240,22 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->phat = phat;
     st->pcm16 = pcm16;
     st->continuous = continuous;
+    st->f16 = f16;
     // <= 2^30 * 2^24; an 8-bit trigger's variance is the firmware's POWER_THRESHOLD (sample_compute.h:21)
     st->thr = continuous ? var * (int64_t)N * N : (pcm16 ? trigger_var : 2) * (int64_t)(N / 2) * (N / 2);
     if (phat) {
         st->phat_eps = tdoa_ctx_phat_eps(ctx);
         // TDOA_STREAM_PHAT_GRID=n caps k_stream_phat's launch size (A/B runs)
+        // (of the long-frame route: both its launches)
         const char *cap = std::getenv("TDOA_STREAM_PHAT_GRID");
-        st->phat_grid = tdoa_stream_phat_grid(kp, num_streams, cap ? std::atoi(cap) : 0, pcm16);
+        const int gcap = cap ? std::atoi(cap) : 0;
+        st->phat_grid = f16 ? tdoa_stream_ema_grid_size(kp, num_streams, gcap)
+                            : tdoa_stream_phat_grid(kp, num_streams, gcap, pcm16);
+        if (f16) {
+            st->f16_grid = tdoa_f16_ring_grid(kp, num_streams, gcap, pcm16);
+            if (st->f16_grid < 1)
+                return tdoa_fail(TDOA_ERR_HIP, "%s: k_f16_ring: no resident workgroup (LDS / registers)", fn);
+        }
     }
     const size_t S = (size_t)num_streams;
     // carve: 256-B aligned sub-buffers of one allocation
@@ -235,7 +270,8 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
                  o_end = take(S * 8), o_at = take(S * 8),
                  o_fresh = take(phat ? 0 : S * P * K * 8), o_fl = take(phat ? 0 : S * P * 4),
                  o_fg = take(phat ? 0 : S), o_est = take(S * P * K * (phat ? 4 : 8)), o_last = take(S * 8),
-                 o_stats = take(16);
+                 o_stats = take(16), o_fw = take(f16 ? S * P * K * 4 : 0), o_fll = take(f16 ? S * P * 4 : 0),
+                 o_fgt = take(f16 ? S : 0);
     if (st->mem.alloc(off) != hipSuccess)
         return tdoa_fail(TDOA_ERR_NOMEM, "%s: %zu bytes of stream state", fn, off);
     char *b = st->mem.get<char>();
@@ -260,6 +296,11 @@ int stream_create(const char *fn, tdoa_ctx *ctx, int32_t num_streams, int32_t ho
     st->est_f = phat ? (float *)(b + o_est) : nullptr;
     sp.last = (uint64_t *)(b + o_last);
     sp.stats = (int64_t *)(b + o_stats);
+    if (f16) {
+        st->f16_w = (float *)(b + o_fw);
+        st->f16_lags = (int32_t *)(b + o_fll);
+        st->f16_gate = (uint8_t *)(b + o_fgt);
+    }
     if (hipMemset(st->mem.get<void>(), 0, off) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
         return tdoa_fail(TDOA_ERR_HIP, "%s: clearing state failed", fn);
     *out = st.release();
@@ -482,6 +523,21 @@ extern "C" int tdoa_stream_peaks(tdoa_stream *st, const tdoa_peaks_params *prm, 
         return rc;
     return tdoa_launch_ls_stream(st->kp, est, st->phat, st->sp.ids, count, st->S, k.lags, k.cell, out->xy_ls,
                                  out->ls_rms, Kp, stream);
+}
+
+extern "C" const char *tdoa_stream_kernel(const tdoa_stream *st)
+{
+    if (!st)
+        return nullptr;
+    if (st->phat)
+        return st->f16 ? "k_f16_ring" : (st->pcm16 ? "k_stream_phat_pcm16" : "k_stream_phat");
+    tdoa_kparams kp = st->kp;  // as enqueue_step launches DIRECT: frames staged from the rings
+    kp.frame_ids = st->sp.ids;
+    kp.frame_ring = st->sp.capture;
+    kp.ring_len = st->sp.capture_len;
+    kp.frame_end = st->sp.end;
+    kp.frame_ring_at = st->sp.ring_at;
+    return tdoa_direct_ema_fits(kp) ? "k_direct_mfma" : "k_direct";
 }
 
 extern "C" int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is_float)

@@ -19,6 +19,10 @@
 //                  (fp32, no contraction; now = end * 1e6 / fs), the EMA rows'
 //                  first maxima and the grid solve on the EMA scores over the
 //                  distinct lag tuples (float L, first tuple on ties).
+//   k_stream_ema_grid  the part after the lag prior alone, for the long-frame
+//                  shapes whose scores k_f16_ring (tdoa_phat_r16.hip) computes:
+//                  it reads each slot's lags, gate and weighted scores from a
+//                  scratch in place of LDS.  One text: tdoa_stream_ema_grid.inc.
 //
 // Every stage from the front end to the lag prior is a function of
 // tdoa_phat_lds.h, the one k_phat_spectra and k_phat_pairs call, so a frame's
@@ -79,7 +83,9 @@ __global__ void __launch_bounds__(TPB) k_stream_phat(tdoa_stream_params sp, tdoa
                                                      float *__restrict__ est_all, float *__restrict__ max_Lf,
                                                      int nstreams, float e2)
 {
-    constexpr bool PCM16 = false;
+    constexpr bool PCM16 = false, SCRATCH = false;
+    constexpr const int32_t *lags_in = nullptr;  // (SCRATCH only)
+    constexpr const uint8_t *gate_in = nullptr;
 #include "tdoa_stream_phat_hop.inc"
 }
 
@@ -88,8 +94,53 @@ __global__ void __launch_bounds__(TPB) k_stream_phat_pcm16(tdoa_stream_params sp
                                                            tdoa_stream_kout out, float *__restrict__ est_all,
                                                            float *__restrict__ max_Lf, int nstreams, float e2)
 {
-    constexpr bool PCM16 = true;
+    constexpr bool PCM16 = true, SCRATCH = false;
+    constexpr const int32_t *lags_in = nullptr;  // (SCRATCH only)
+    constexpr const uint8_t *gate_in = nullptr;
 #include "tdoa_stream_phat_hop.inc"
+}
+
+// The hop's second half for the long-frame shapes, after k_f16_ring
+// (tdoa_phat_r16.hip) left every listed slot's lags, gate and weighted scores
+// [S][P][K] in global memory: one 256-thread workgroup per slot, persistent over
+// the device-side count; record, float EMA, EMA rows' maxima and the grid scan
+// are tdoa_stream_ema_grid.inc, the text k_stream_phat runs.  Workgroup 0 does
+// the step's bookkeeping as k_stream_phat does.
+__global__ void __launch_bounds__(TPB) k_stream_ema_grid(tdoa_stream_params sp, tdoa_kparams kp, tdoa_stream_kout out,
+                                                         float *__restrict__ est_all, float *__restrict__ max_Lf,
+                                                         const float *__restrict__ weighted,
+                                                         const int32_t *__restrict__ lags_in,
+                                                         const uint8_t *__restrict__ gate_in, int nstreams)
+{
+    constexpr bool SCRATCH = true;
+    constexpr const int *lag_s = nullptr;  // (LDS kernels only)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int P = kp.P, K = kp.K, S = kp.S, tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6, nwaves = TPB / 64;
+    float *E = (float *)smem;  // [P][K] the stream's EMA scores
+    __shared__ float redv[TPB / 64];
+    __shared__ int redi[TPB / 64];
+    // at most one slot per stream: a corrupted counter cannot index past [S]
+    const int cnt_raw = *sp.count;
+    const int cnt = cnt_raw < 0 ? 0 : (cnt_raw > nstreams ? nstreams : cnt_raw);
+    if (blockIdx.x == 0 && tid == 0) {
+        *sp.pos += sp.H;  // the selector has read it
+        sp.stats[0] += cnt;
+        if (out.count)
+            *out.count = cnt;
+    }
+    int ngated = 0;  // this workgroup's gated frames
+    for (int slot = blockIdx.x; slot < cnt; slot += gridDim.x) {
+        __syncthreads();  // the previous slot's scores and reductions are consumed
+        int s = sp.ids[slot];
+        s = s < 0 ? 0 : (s >= nstreams ? nstreams - 1 : s);  // k_f16_ring's clamp
+        const int64_t end = sp.end[slot];
+        const float *Wf = weighted + (size_t)slot * P * K;
+#include "tdoa_stream_ema_grid.inc"
+    }
+    // gated frames of this hop: one atomic per workgroup that had any
+    if (tid == 0 && ngated)
+        atomicAdd(reinterpret_cast<unsigned long long *>(sp.stats + 1), (unsigned long long)ngated);
 }
 
 }  // namespace
@@ -129,6 +180,28 @@ int tdoa_stream_phat_grid(const tdoa_kparams &kp, int64_t S, int cap, bool pcm16
     if (cap > 0 && grid > cap)
         grid = cap;
     return (int)(grid > 0 ? grid : 1);
+}
+
+int tdoa_stream_ema_grid_size(const tdoa_kparams &kp, int64_t S, int cap)
+{
+    const int res = tdoa_resident_blocks((const void *)k_stream_ema_grid, TPB, (size_t)kp.P * kp.K * sizeof(float));
+    int64_t grid = S;
+    if (res > 0 && grid > res)
+        grid = res;
+    if (cap > 0 && grid > cap)
+        grid = cap;
+    return (int)(grid > 0 ? grid : 1);
+}
+
+int tdoa_launch_stream_ema_grid(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,
+                                float *est, float *max_Lf, const float *weighted, const int32_t *lags,
+                                const uint8_t *gate, int64_t S, int grid, void *stream)
+{
+    hipLaunchKernelGGL(k_stream_ema_grid, dim3((unsigned)(grid > 0 ? grid : 1)), dim3(TPB),
+                       (size_t)kp.P * kp.K * sizeof(float), (hipStream_t)stream, sp, kp, out, est, max_Lf, weighted,
+                       lags, gate, (int)S);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : tdoa_hip_fail(e, "k_stream_ema_grid launch");
 }
 
 int tdoa_launch_stream_phat(const tdoa_stream_params &sp, const tdoa_kparams &kp, const tdoa_stream_kout &out,

@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_heatmap", "tdoa_peaks", "tdoa_stream_create", "tdoa_stream_step", "tdoa_stream_reset", "tdoa_stream_state",
     "tdoa_stream_destroy", "tdoa_stream_step_f", "tdoa_stream_state_f", "tdoa_stream_create_pcm16",
     "tdoa_stream_create_continuous", "tdoa_stream_peaks", "tdoa_stream_est_device",
+    "tdoa_stream_kernel",
     "tdoa_track_batch", "tdoa_track_host", "tdoa_stream_track", "tdoa_stream_tracks_device",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
@@ -219,6 +220,8 @@ def load() -> C.CDLL:
     L.tdoa_stream_destroy.argtypes = [P]
     L.tdoa_stream_peaks.argtypes = [P, C.POINTER(PeaksParams), P, C.POINTER(PeaksOutputs), P]
     L.tdoa_stream_est_device.argtypes = [P, C.POINTER(P), C.POINTER(C.c_int)]
+    L.tdoa_stream_kernel.argtypes = [P]
+    L.tdoa_stream_kernel.restype = C.c_char_p
     track_tail = [P, I32, C.POINTER(TrackParams), C.POINTER(TrackOutputs)]  # xy, Kp, prm, out
     L.tdoa_track_batch.argtypes = [C.c_int, P, P, I64, P, P, P] + track_tail + [P]
     L.tdoa_track_host.argtypes = [P, P, I64, P, P, P] + track_tail

@@ -13,6 +13,12 @@ float scores under the localizer's weight table (set_band / set_bin_weights,
 read at every step), a float32 EMA, `out["max_Lf"]` in place of
 `out["max_L"]` and float32 `est` from state().
 
+The shapes k_stream_phat's LDS cannot hold but the batch engine's long-frame
+kernel can -- 8 mics x 2048 and 4 mics x 4096 -- stream through k_f16_ring
+(that kernel's body over the step's listed frames, staged from the rings) and
+k_stream_ema_grid, in every mode and ring format below; `kernel` names the
+route.  Records, state, peaks() and track() are the same.
+
 A `gcc_phat` Localizer whose sample_format is "pcm16" streams an int16 capture
 ring [S][capture_len][M] (tdoa_stream_create_pcm16: k_stream_trigger16, then
 k_stream_phat_pcm16): the trigger of include/tdoa.h on int16 samples with the
@@ -313,6 +319,13 @@ class StreamPipeline:
                 if rc != 0:
                     raise RuntimeError(f"copying the track state failed: hipError {rc}")
         return tracks, next_id
+
+    @property
+    def kernel(self) -> str:
+        """Name of the kernel that computes the hop's scores (tdoa_stream_kernel):
+        k_stream_phat / k_stream_phat_pcm16, k_f16_ring for the long-frame
+        shapes (8 mics x 2048, 4 x 4096), k_direct_mfma / k_direct."""
+        return (load().tdoa_stream_kernel(self._h) or b"").decode()
 
     def est_ptr(self):
         """(device address, is_float) of the EMA state: int64 [S][P][K] (DIRECT)

@@ -345,9 +345,19 @@ int tdoa_dpss_q15(int32_t n, double nw, int32_t *out);
  * tdoa_stream_state_f; tdoa_stream_step, and tdoa_stream_state with a non-NULL
  * est, return TDOA_ERR_INVALID on it, as the _f forms do on a DIRECT one.
  * Accepted GCC_PHAT shapes: M * N * 8 + N * 8 + 2 * P * K * 4 bytes of LDS
- * within 160 KiB (4 mics up to frame_len 2048, 8 mics up to 1024, ...);
- * others are TDOA_ERR_INVALID.  TDOA_STREAM_PHAT_GRID=n in the environment at
- * tdoa_stream_create caps the GCC_PHAT kernel's launch size (A/B runs). */
+ * within 160 KiB (4 mics up to frame_len 2048, 8 mics up to 1024, 3 mics up to
+ * 4096, ...: kernel k_stream_phat), and the two long-frame shapes beyond that
+ * rule which the batch engine's per-frame kernel holds, 8 mics x 2048 and
+ * 4 mics x 4096: there the hop is k_f16_ring (that kernel's body over the
+ * step's listed frames, staged from the capture rings; its scores are the batch
+ * call's for the same frame, and the weight table in force applies as above)
+ * followed by k_stream_ema_grid (record, EMA, grid solve).  Records, state,
+ * tdoa_stream_peaks and tdoa_stream_track are the same on either route; at the
+ * two long-frame shapes a stream's ring (capture_len * M samples) must stay
+ * under 2^31 bytes.  Other shapes (8 mics x 4096, ...) are TDOA_ERR_INVALID.
+ * tdoa_stream_kernel names the route.  TDOA_STREAM_PHAT_GRID=n in the
+ * environment at tdoa_stream_create caps the GCC_PHAT kernels' launch sizes
+ * (A/B runs). */
 typedef struct tdoa_stream tdoa_stream;
 
 typedef struct tdoa_stream_outputs { /* device pointers; slot order is arbitrary */
@@ -408,11 +418,14 @@ int tdoa_stream_create(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
  * The result is an ordinary tdoa_stream: it steps with tdoa_stream_step_f, is
  * read with tdoa_stream_state_f (and tdoa_stream_state with est = NULL), and
  * tdoa_stream_reset / tdoa_stream_destroy apply; graph mode and plain stream
- * launches both work.  Kernels: k_stream_trigger16, k_stream_phat_pcm16.
+ * launches both work.  Kernels: k_stream_trigger16, k_stream_phat_pcm16 (at
+ * 8 mics x 2048 and 4 mics x 4096: k_f16_ring on the int16 ring, then
+ * k_stream_ema_grid).
  * TDOA_ERR_INVALID, with tdoa_last_error naming the cause: a DIRECT context; a
  * GCC_PHAT context in ADC8 format; trigger_var outside [0, 2^30]; hop outside
- * [1, N]; capture_len < N + 2 hop; a shape outside the GCC_PHAT LDS rule above
- * or whose trigger needs more than 150 KiB of LDS
+ * [1, N]; capture_len < N + 2 hop; a shape outside the GCC_PHAT shapes above
+ * (the LDS rule and the two long-frame shapes) or whose trigger needs more than
+ * 150 KiB of LDS
  * (2 M (N + hop - 1) + 12 (N + hop) bytes). */
 #define TDOA_STREAM_TRIGGER_VAR_PCM16 131072 /* 2 * 256^2: the 8-bit threshold for samples scaled by 256 */
 int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
@@ -445,7 +458,8 @@ int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
  * ((-32768)^2 * 4 = 2^32 does not fit) and in 64 bits from there.
  * Each listed frame goes through exactly what a triggered frame does
  * (k_stream_phat staging it from the ring, or k_stream_phat_pcm16 with the
- * PCM16 front end): PHAT with phat_eps, the context's bin-weight table read at
+ * PCM16 front end; at 8 mics x 2048 and 4 mics x 4096 k_f16_ring and
+ * k_stream_ema_grid, either ring type): PHAT with phat_eps, the context's bin-weight table read at
  * every step, the inverses, first maximum, prior, the gate sum_p lag^2 > 4
  * deciding whether the EMA updates, the float EMA with now_us = e * 1e6 / fs,
  * and the grid solve on the EMA scores.
@@ -457,8 +471,9 @@ int tdoa_stream_create_pcm16(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
  * TDOA_ERR_INVALID, with tdoa_last_error naming the cause: a NULL argument; a
  * DIRECT context (it reproduces the firmware, which has no such mode);
  * activity_var outside [0, 2^30]; hop outside [1, N]; capture_len < N + 2 hop;
- * an int16 ring that is not 2-byte aligned; a shape outside the GCC_PHAT LDS
- * rule above.  The triggers' own 150 KiB LDS limit does not apply. */
+ * an int16 ring that is not 2-byte aligned; a shape outside the GCC_PHAT
+ * shapes above (the LDS rule and the two long-frame shapes).  The triggers' own
+ * 150 KiB LDS limit does not apply. */
 int tdoa_stream_create_continuous(tdoa_ctx *ctx, int32_t num_streams, int32_t hop,
                                   const void *capture /* device [S][capture_len][M] */,
                                   int64_t capture_len, int64_t activity_var, int use_graph,
@@ -533,6 +548,11 @@ int tdoa_stream_peaks(tdoa_stream *st, const tdoa_peaks_params *prm,
  * not only the listed ones; such calls follow the usual rule: stream-ordered
  * with the steps.  Host only; TDOA_ERR_INVALID for a NULL argument. */
 int tdoa_stream_est_device(tdoa_stream *st, const void **est, int *is_float);
+/* Name of the kernel that computes the hop's scores (diagnostics, like
+ * tdoa_batch_kernel): "k_stream_phat" / "k_stream_phat_pcm16", "k_f16_ring" at
+ * the long-frame shapes (either ring type), "k_direct_mfma" / "k_direct" for a
+ * DIRECT pipeline.  A static string; NULL for a NULL st. */
+const char *tdoa_stream_kernel(const tdoa_stream *st);
 
 /* ---- Tracking: sources followed across hops from the per-hop peaks ----
  * The rows tdoa_stream_peaks (or tdoa_peaks) reports are unlabelled and

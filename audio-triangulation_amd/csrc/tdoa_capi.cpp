@@ -8,6 +8,7 @@
 // one, reached through the launchers of tdoa_internal.h).
 
 #include "../../include/tdoa.h"
+#include "tdoa_beam_rule.h"
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
 #include "tdoa_tables.h"
@@ -51,6 +52,11 @@ struct tdoa_ctx {
     // none) and its device copy, [N + 1] floats, kept once allocated
     std::vector<float> bin_w;
     tdoa_devmem d_bin_w;
+    // the beamformer (tdoa_beam_batch, tdoa_stream_beam): what steering reads of
+    // the config, the largest inter-mic delay, the FIR table's device copy
+    tdoa_beam_geometry beam_g;
+    int beam_dmax = 0;
+    tdoa_devmem beam_fir;
     tdoa_kparams kp;
 };
 
@@ -163,6 +169,29 @@ int upload_grid(tdoa_ctx *c)
     return TDOA_OK;
 }
 
+// the beamformer's geometry (the tables' mics and the config's scalars), its
+// largest delay, and the FIR table
+int upload_beam(tdoa_ctx *c)
+{
+    const tdoa_tables &t = c->t;
+    tdoa_beam_geometry &g = c->beam_g;
+    std::memset(&g, 0, sizeof g);
+    g.num_mics = t.M;
+    g.sample_rate_hz = t.cfg.sample_rate_hz;
+    g.speed_of_sound = t.cfg.speed_of_sound;
+    g.height_offset = t.cfg.height_offset;
+    std::memcpy(&g.mic_xy[0][0], t.mic.data(), vbytes(t.mic));
+    // a geometry the beamformer cannot take (mics further apart than 65535
+    // samples, a non-finite coordinate) leaves beam_dmax 0: its calls say why
+    if (tdoa_beam_dmax(g, &c->beam_dmax) != TDOA_OK)
+        c->beam_dmax = 0;
+    float fir[TDOA_BEAM_PHASES * TDOA_BEAM_TAPS];
+    tdoa_beam_fir(fir);
+    if (c->beam_fir.upload(fir, sizeof fir) != hipSuccess)
+        return tdoa_fail(TDOA_ERR_NOMEM, "uploading the beamformer's FIR table failed");
+    return TDOA_OK;
+}
+
 // the kernel parameters: the tables' scalars, then every device pointer
 void wire_kparams(tdoa_ctx *c)
 {
@@ -221,6 +250,8 @@ extern "C" int tdoa_create(const tdoa_config *cfg, int device, tdoa_ctx **out)
     if (const int rc = upload_gcc_phat(c.get()))
         return rc;
     if (const int rc = upload_grid(c.get()))
+        return rc;
+    if (const int rc = upload_beam(c.get()))
         return rc;
     wire_kparams(c.get());
     *out = c.release();
@@ -507,6 +538,55 @@ int tdoa_ctx_device(const tdoa_ctx *c) { return c->device; }
 int tdoa_ctx_engine(const tdoa_ctx *c) { return c->t.cfg.engine; }
 int tdoa_ctx_rate(const tdoa_ctx *c) { return c->t.cfg.sample_rate_hz; }
 float tdoa_ctx_phat_eps(const tdoa_ctx *c) { return c->t.cfg.phat_eps; }
+
+int tdoa_ctx_beam(const tdoa_ctx *c, const char *fn, tdoa_beam_geometry *g, int *Dmax, const float **fir)
+{
+    if (c->beam_dmax <= 0) {
+        int d = 0;
+        const int rc = tdoa_beam_dmax(c->beam_g, &d);  // stores the cause
+        return rc ? rc : tdoa_fail(TDOA_ERR_INVALID, "%s: the context has no beamformer geometry", fn);
+    }
+    *g = c->beam_g;
+    *Dmax = c->beam_dmax;
+    *fir = c->beam_fir.get<float>();
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_beam_latency(const tdoa_ctx *ctx, int32_t *A, int32_t *Dmax)
+{
+    if (!ctx)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_latency: NULL ctx");
+    return tdoa_beam_latency_of(&ctx->beam_g, A, Dmax);
+}
+
+extern "C" int tdoa_get_beam_geometry(const tdoa_ctx *ctx, tdoa_beam_geometry *g)
+{
+    if (!ctx || !g)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_get_beam_geometry: NULL argument");
+    *g = ctx->beam_g;
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_beam_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count,
+                               const float *xy, int32_t Kt, const tdoa_beam_outputs *out, void *stream)
+{
+    if (!ctx || !frames || !xy || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_batch: NULL argument");
+    tdoa_beam_geometry g;
+    int Dmax = 0;
+    const float *fir = nullptr;
+    if (const int rc = tdoa_ctx_beam(ctx, "tdoa_beam_batch", &g, &Dmax, &fir))
+        return rc;
+    if (const int rc = tdoa_beam_check("tdoa_beam_batch", g, Dmax, ctx->t.N, Kt, out, out->audio, true))
+        return rc;
+    if (B < 0 || B >= ((int64_t)1 << 31))
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_batch: B %lld outside [0, 2^31)", (long long)B);
+    if (B == 0)
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return tdoa_launch_beam(g, Dmax, frames, true, 0, nullptr, B, ctx->t.N, count, xy, nullptr, 0, Kt, fir, *out,
+                            stream);
+}
 
 extern "C" int tdoa_localize_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B,
                                    const tdoa_outputs *out, void *stream)

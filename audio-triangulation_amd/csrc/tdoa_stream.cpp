@@ -26,6 +26,7 @@
 #include <memory>
 
 #include "../../include/tdoa.h"
+#include "tdoa_beam_rule.h"
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
 #include "tdoa_track_rule.h"
@@ -587,6 +588,35 @@ extern "C" int tdoa_stream_tracks_device(tdoa_stream *st, const tdoa_track **tra
     *tracks = t;
     *next_id = t ? reinterpret_cast<const int32_t *>(t + (size_t)st->S * TDOA_MAX_TRACKS) : nullptr;
     return TDOA_OK;
+}
+
+extern "C" int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt,
+                                int32_t min_status, const tdoa_beam_outputs *out, void *stream)
+{
+    if (!st || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_beam: NULL argument");
+    tdoa_beam_geometry g;
+    int Dmax = 0;
+    const float *fir = nullptr;
+    if (const int rc = tdoa_ctx_beam(st->ctx, "tdoa_stream_beam", &g, &Dmax, &fir))
+        return rc;
+    const int hop = st->sp.H, A = Dmax + TDOA_BEAM_HALF;
+    if (const int rc = tdoa_beam_check("tdoa_stream_beam", g, Dmax, hop, Kt, out, out->audio, true))
+        return rc;
+    if (!xy && !st->track_mem)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_beam: no xy and no track table yet (tdoa_stream_track "
+                                           "makes it)");
+    // a block reaches hop + A + 7 samples back from the clock and Dmax + 8 past
+    // its last output; one more hop is the producer's margin
+    const int64_t need = 2 * (int64_t)hop + A + Dmax + 16;
+    if (st->sp.capture_len < need)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_beam: capture_len %lld < 2 hop + A + Dmax + 16 = %lld",
+                         (long long)st->sp.capture_len, (long long)need);
+    if (st->hop == 0)  // no step since creation or reset: the clock has not moved
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(st->device));
+    return tdoa_launch_beam(g, Dmax, st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S, hop, count, xy,
+                            xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt, fir, *out, stream);
 }
 
 extern "C" int tdoa_stream_destroy(tdoa_stream *st)

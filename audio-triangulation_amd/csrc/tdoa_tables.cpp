@@ -682,3 +682,70 @@ int tdoa_build_tables(const tdoa_config *cfg, tdoa_tables *c)
 #endif
     return TDOA_OK;
 }
+
+// ---------------------------------------------------------------- beamformer
+// The fractional-delay FIR table of include/tdoa.h ("Listening"): 32 phases of
+// a 16-tap Kaiser-windowed sinc (beta 8), each normalised to sum 1, in double.
+namespace {
+
+// modified Bessel function I0 by its power series: terms ((x/2)^k / k!)^2
+double bessel_i0(double x)
+{
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; k++) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+        if (term < 1e-18 * sum)
+            break;
+    }
+    return sum;
+}
+
+}  // namespace
+
+extern "C" int tdoa_beam_fir(float *h)
+{
+    if (!h)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_fir: NULL");
+    const double pi = 3.14159265358979323846, beta = (double)TDOA_BEAM_HALF, i0b = bessel_i0(beta);
+    for (int q = 0; q < TDOA_BEAM_PHASES; q++) {
+        double w[2 * TDOA_BEAM_HALF], sum = 0.0;
+        for (int i = 0; i < 2 * TDOA_BEAM_HALF; i++) {
+            const int k = i - (TDOA_BEAM_HALF - 1);
+            const double x = (double)k - (double)q / TDOA_BEAM_PHASES, r = x / TDOA_BEAM_HALF;
+            // (at phase 0 x is an integer: the sinc is the unit tap itself, no sin(pi k) residue)
+            const double sinc = q == 0 ? (k == 0 ? 1.0 : 0.0) : std::sin(pi * x) / (pi * x);
+            w[i] = r * r <= 1.0 ? sinc * bessel_i0(beta * std::sqrt(1.0 - r * r)) / i0b : 0.0;
+            sum += w[i];
+        }
+        for (int i = 0; i < 2 * TDOA_BEAM_HALF; i++)
+            h[q * 2 * TDOA_BEAM_HALF + i] = (float)(w[i] / sum);
+    }
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_beam_geometry_of(const tdoa_config *cfg, tdoa_beam_geometry *g)
+{
+    if (!cfg || !g)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_geometry_of: NULL argument");
+    const int M = cfg->num_mics;
+    if (M < 2 || M > TDOA_MAX_MICS)
+        return tdoa_fail(TDOA_ERR_INVALID, "num_mics %d outside [2,%d]", M, TDOA_MAX_MICS);
+    if (cfg->sample_rate_hz <= 0 || !(cfg->speed_of_sound > 0))
+        return tdoa_fail(TDOA_ERR_INVALID, "sample_rate_hz / speed_of_sound must be positive");
+    if (!(cfg->height_offset > 0))
+        return tdoa_fail(TDOA_ERR_INVALID, "bad grid geometry");
+    if (M != 3 && !cfg->mic_xy)
+        return tdoa_fail(TDOA_ERR_INVALID, "mic_xy is required unless num_mics == 3");
+    std::memset(g, 0, sizeof *g);
+    g->num_mics = M;
+    g->sample_rate_hz = cfg->sample_rate_hz;
+    g->speed_of_sound = cfg->speed_of_sound;
+    g->height_offset = cfg->height_offset;
+    if (cfg->mic_xy)
+        std::memcpy(&g->mic_xy[0][0], cfg->mic_xy, sizeof(float) * 2 * M);
+    else
+        reference_triangle(&g->mic_xy[0][0]);
+    return TDOA_OK;
+}

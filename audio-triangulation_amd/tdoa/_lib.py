@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "tdoa_stream_create_continuous", "tdoa_stream_peaks", "tdoa_stream_est_device",
     "tdoa_stream_kernel",
     "tdoa_track_batch", "tdoa_track_host", "tdoa_stream_track", "tdoa_stream_tracks_device",
+    "tdoa_beam_fir", "tdoa_beam_geometry_of", "tdoa_beam_latency_of", "tdoa_beam_latency", "tdoa_get_beam_geometry",
+    "tdoa_beam_batch", "tdoa_beam_host", "tdoa_stream_beam",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -138,6 +140,20 @@ class TrackOutputs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("tracks", "assigned", "num_confirmed")]
 
 
+BEAM_HALF, BEAM_PHASES, BEAM_MAX_TARGETS = 8, 32, 8  # TDOA_BEAM_HALF, TDOA_BEAM_PHASES, TDOA_BEAM_MAX_TARGETS
+
+
+class BeamGeometry(C.Structure):
+    """struct tdoa_beam_geometry (include/tdoa.h): what steering reads of a context."""
+    _fields_ = [("num_mics", C.c_int32), ("sample_rate_hz", C.c_int32), ("speed_of_sound", C.c_float),
+                ("height_offset", C.c_float), ("mic_xy", C.c_float * 16)]
+
+
+class BeamOutputs(C.Structure):
+    """struct tdoa_beam_outputs (include/tdoa.h): audio is required."""
+    _fields_ = [(n, C.c_void_p) for n in ("audio", "delays", "active", "block_start")]
+
+
 class StreamOutputs(C.Structure):
     """struct tdoa_stream_outputs (include/tdoa.h): device pointers."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -227,6 +243,14 @@ def load() -> C.CDLL:
     L.tdoa_track_host.argtypes = [P, P, I64, P, P, P] + track_tail
     L.tdoa_stream_track.argtypes = [P, C.POINTER(TrackParams), P] + track_tail[:2] + [C.POINTER(TrackOutputs), P]
     L.tdoa_stream_tracks_device.argtypes = [P, C.POINTER(P), C.POINTER(P)]
+    L.tdoa_beam_fir.argtypes = [P]
+    L.tdoa_beam_geometry_of.argtypes = [C.POINTER(Config), C.POINTER(BeamGeometry)]
+    L.tdoa_beam_latency_of.argtypes = [C.POINTER(BeamGeometry), C.POINTER(I32), C.POINTER(I32)]
+    L.tdoa_beam_latency.argtypes = [P, C.POINTER(I32), C.POINTER(I32)]
+    L.tdoa_get_beam_geometry.argtypes = [P, C.POINTER(BeamGeometry)]
+    L.tdoa_beam_batch.argtypes = [P, P, I64, P, P, I32, C.POINTER(BeamOutputs), P]
+    L.tdoa_beam_host.argtypes = [C.POINTER(BeamGeometry), I32, P, I64, P, P, I32, C.POINTER(BeamOutputs)]
+    L.tdoa_stream_beam.argtypes = [P, P, P, I32, I32, C.POINTER(BeamOutputs), P]
     L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
     L.tdoa_set_bin_weights.argtypes = [P, P]
     L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]
@@ -323,4 +347,75 @@ def track_host(tracks, next_id, t_us, count, xy, stream_of_row=None, **params) -
     out = TrackOutputs(*[ptr(o[n]) for n, _ in TrackOutputs._fields_])
     check(load().tdoa_track_host(ptr(tracks), ptr(next_id), rows, None if sor is None else ptr(sor), ptr(t_us),
                                  ptr(count), ptr(xy), Kp, C.byref(prm), C.byref(out)), "tdoa_track_host")
+    return o
+
+
+def beam_fir():
+    """The beamformer's fractional-delay FIR table (tdoa_beam_fir): float32
+    [32][16], phase q, tap k = -7..8 at [q][k + 7].  Host only."""
+    import numpy as np
+    h = np.zeros((BEAM_PHASES, 2 * BEAM_HALF), np.float32)
+    check(load().tdoa_beam_fir(h.ctypes.data_as(C.c_void_p)), "tdoa_beam_fir")
+    return h
+
+
+def beam_geometry(mic_xy=None, num_mics: int = 3, sample_rate_hz: int = 50000, speed_of_sound: float = 343.0,
+                  height_offset: float = 1.2) -> BeamGeometry:
+    """BeamGeometry of the context these config fields would make
+    (tdoa_beam_geometry_of): mic_xy [M][2] metres, None with 3 mics for the
+    reference triangle.  Host only."""
+    import numpy as np
+    cfg = Config()
+    check(load().tdoa_config_default(C.byref(cfg)), "tdoa_config_default")
+    mics = None
+    if mic_xy is not None:
+        mics = np.ascontiguousarray(mic_xy, np.float32)
+        if mics.ndim != 2 or mics.shape[1] != 2:
+            raise ValueError("mic_xy must be [M][2]")
+        num_mics = mics.shape[0]
+        cfg.mic_xy = mics.ctypes.data_as(C.POINTER(C.c_float))
+    cfg.num_mics, cfg.sample_rate_hz = int(num_mics), int(sample_rate_hz)
+    cfg.speed_of_sound, cfg.height_offset = float(speed_of_sound), float(height_offset)
+    g = BeamGeometry()
+    check(load().tdoa_beam_geometry_of(C.byref(cfg), C.byref(g)), "tdoa_beam_geometry_of")
+    return g
+
+
+def beam_latency(geometry: BeamGeometry):
+    """(A, Dmax) of a geometry in samples (tdoa_beam_latency_of): output sample
+    n needs the input up to n + A; no delay code exceeds 32 Dmax."""
+    a, d = C.c_int32(), C.c_int32()
+    check(load().tdoa_beam_latency_of(C.byref(geometry), C.byref(a), C.byref(d)), "tdoa_beam_latency_of")
+    return a.value, d.value
+
+
+def beam_host(geometry: BeamGeometry, frames, xy, count=None) -> dict:
+    """tdoa_beam_host: the beamformer's rule (include/tdoa.h, "Listening") on
+    numpy arrays, no device.  frames int16 [B][M][N] (any N >= 1), xy float32
+    [B][Kt][2] plane coordinates, count int32 [B] (None: all Kt).  Returns audio
+    float32 [B][Kt][N], delays int32 [B][Kt][M] (the codes, -1 invalid) and
+    active uint8 [B][Kt]."""
+    import numpy as np
+    frames = np.ascontiguousarray(frames, np.int16)
+    xy = np.ascontiguousarray(xy, np.float32)
+    M = geometry.num_mics
+    if frames.ndim != 3 or frames.shape[1] != M:
+        raise ValueError(f"frames must be int16 [B][{M}][N]")
+    B, _, N = frames.shape
+    if xy.ndim != 3 or xy.shape[0] != B or xy.shape[2] != 2:
+        raise ValueError("xy must be [B][Kt][2]")
+    Kt = xy.shape[1]
+    if count is not None:
+        count = np.ascontiguousarray(count, np.int32)
+        if count.shape != (B,):
+            raise ValueError("count must be [B]")
+    o = {"audio": np.zeros((B, Kt, N), np.float32), "delays": np.zeros((B, Kt, M), np.int32),
+         "active": np.zeros((B, Kt), np.uint8)}
+    stub = np.zeros(1, np.int64)  # B = 0: an empty array's address may be NULL, and nothing is read
+
+    def ptr(a):
+        return (a if a.size else stub).ctypes.data_as(C.c_void_p)
+    out = BeamOutputs(ptr(o["audio"]), ptr(o["delays"]), ptr(o["active"]), None)
+    check(load().tdoa_beam_host(C.byref(geometry), N, ptr(frames), B, None if count is None else ptr(count), ptr(xy),
+                                Kt, C.byref(out)), "tdoa_beam_host")
     return o

@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Config, Outputs, PeaksOutputs, PeaksParams, TrackOutputs, check, load, track_params
+from ._lib import (BeamGeometry, BeamOutputs, Config, Outputs, PeaksOutputs, PeaksParams, TrackOutputs, check, load,
+                   track_params)
 
 
 def _ptr(t: torch.Tensor | None):
@@ -407,6 +408,62 @@ class Localizer:
                                       _ptr(count), _ptr(xy), Kp, C.byref(prm), C.byref(o),
                                       C.c_void_p(st.cuda_stream)), "tdoa_track_batch")
         return outputs
+
+    def beam_batch(self, frames: torch.Tensor, xy: torch.Tensor, count: torch.Tensor | None = None,
+                   outputs=None, stream=None) -> dict:
+        """Beamformed audio of up to 8 targets per frame (tdoa_beam_batch, kernel
+        k_beam; the rule is in include/tdoa.h, "Listening").
+
+        frames: int16 [B][M][N] as localize() takes them; xy: float32
+        [B][Kt][2] plane coordinates (a localize() xy / xy_ls, a peaks() row);
+        count: int32 [B], target k of frame b valid for k < count[b] (None: all
+        Kt) and finite coordinates.  outputs: a dict of tensors to write (audio
+        float32 [B][Kt][N], required; delays int32 [B][Kt][M]; active uint8
+        [B][Kt]) -- fresh ones by default.  Asynchronous on `stream` (default:
+        the current stream)."""
+        dev = self.torch_device
+        M, N = self.dims.M, self.dims.N
+        if frames.dtype != torch.int16 or frames.dim() != 3 or tuple(frames.shape[1:]) != (M, N):
+            raise ValueError(f"frames must be int16 [B][{M}][{N}]")
+        B = frames.shape[0]
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != B or xy.shape[2] != 2:
+            raise ValueError("xy must be float32 [B][Kt][2]")
+        Kt = xy.shape[1]
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B,)):
+            raise ValueError("count must be int32 [B]")
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        want = {"audio": (torch.float32, (B, Kt, N)), "delays": (torch.int32, (B, Kt, M)),
+                "active": (torch.uint8, (B, Kt))}
+        if outputs is None:
+            with torch.cuda.stream(st):
+                outputs = {k: torch.empty(shp, dtype=dt, device=dev) for k, (dt, shp) in want.items()}
+        if "audio" not in outputs:
+            raise ValueError("outputs[\"audio\"] is required")
+        for name, t in outputs.items():
+            if name not in want or t.dtype != want[name][0] or tuple(t.shape) != want[name][1]:
+                raise ValueError(f"outputs[{name!r}] must be {want.get(name)}")
+        for t in (frames, xy, count, *outputs.values()):
+            if t is not None and (t.device != dev or not t.is_contiguous()):
+                raise ValueError(f"every tensor must be contiguous on {dev}")
+        if B == 0:  # nothing to launch (and empty tensors have no address to pass)
+            return outputs
+        o = BeamOutputs(*[None if outputs.get(n) is None else outputs[n].data_ptr() for n, _ in BeamOutputs._fields_])
+        check(load().tdoa_beam_batch(self._ctx, _ptr(frames), B, _ptr(count), _ptr(xy) if xy.numel() else None, Kt,
+                                     C.byref(o), C.c_void_p(st.cuda_stream)), "tdoa_beam_batch")
+        return outputs
+
+    def beam_geometry(self) -> BeamGeometry:
+        """What steering reads of this context (tdoa_get_beam_geometry)."""
+        g = BeamGeometry()
+        check(load().tdoa_get_beam_geometry(self._ctx, C.byref(g)), "tdoa_get_beam_geometry")
+        return g
+
+    def beam_latency(self):
+        """(A, Dmax) in samples (tdoa_beam_latency): the beam's output sample n
+        needs the input up to n + A; no delay code exceeds 32 Dmax."""
+        a, d = C.c_int32(), C.c_int32()
+        check(load().tdoa_beam_latency(self._ctx, C.byref(a), C.byref(d)), "tdoa_beam_latency")
+        return a.value, d.value
 
     def cell_xy(self, cell: np.ndarray) -> np.ndarray:
         """((x - half_w)/scale, (half_h - y)/scale) of row-major cells, float32 as on device."""

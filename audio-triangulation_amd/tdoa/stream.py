@@ -71,6 +71,13 @@ every operation rounded on its own and IEEE division, in exactly this order:
 With gated_only=False peaks, a stream never updated reports cell 0 with L = 0
 and a track is born there: track gated peaks (the default) or use min_rel.
 
+beam() listens to the sources (tdoa_stream_beam: k_beam_ring; the rule is in
+include/tdoa.h, "Listening"): per hop and stream one block of delay-and-sum
+audio per target -- the track table's slots (step -> peaks -> track -> beam) or
+explicit plane coordinates -- read from the capture rings behind the device
+clock, for every stream whether the step listed it or not, A = Dmax + 8
+samples behind the clock (Localizer.beam_latency()); consecutive blocks abut.
+
 mode="continuous" (a `gcc_phat` Localizer; tdoa_stream_create_continuous:
 k_stream_active in place of a trigger) chooses frames for continuous audio
 instead of clicks.  The ring is uint8 or int16 according to loc.sample_format.
@@ -89,8 +96,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (MAX_TRACKS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS, PeaksOutputs, PeaksParams, StreamOutputs,
-                   StreamOutputsF, TrackOutputs, check, load, track_params)
+from ._lib import (BEAM_MAX_TARGETS, MAX_TRACKS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS, BeamOutputs, PeaksOutputs,
+                   PeaksParams, StreamOutputs, StreamOutputsF, TrackOutputs, check, load, track_params)
 from .localizer import Localizer
 
 
@@ -176,6 +183,7 @@ class StreamPipeline:
         self._peaks_last = None
         self._tracks = {}  # (T, Kp) -> the output tensors of track()
         self._tracks_last = None
+        self._beams = {}  # Kt -> the output tensors of beam()
 
     def step(self) -> dict:
         """One hop for every stream (asynchronous on self.stream)."""
@@ -326,6 +334,57 @@ class StreamPipeline:
         k_stream_phat / k_stream_phat_pcm16, k_f16_ring for the long-frame
         shapes (8 mics x 2048, 4 x 4096), k_direct_mfma / k_direct."""
         return (load().tdoa_stream_kernel(self._h) or b"").decode()
+
+    def beam(self, xy: torch.Tensor | None = None, count: torch.Tensor | None = None,
+             num_targets: int | None = None, min_status: int = 2) -> dict:
+        """One block of beamformed audio per stream and target
+        (tdoa_stream_beam, kernel k_beam_ring; the rule is in include/tdoa.h,
+        "Listening"), asynchronous on self.stream: call it after step() -- and
+        after peaks() / track() when it listens to their results -- before the
+        producer overwrites the ring rows of the last hop + A + 7 samples.
+
+        xy: float32 [S][Kt][2] plane coordinates indexed by STREAM (scatter a
+        step's peaks by out["stream_id"]), target k of stream s valid for
+        k < count[s] (int32 [S]; None: all Kt) and finite coordinates.  xy None:
+        the pipeline's own track table, channel k = track slot k (k <
+        num_targets, default 8), valid iff its status >= min_status (2:
+        confirmed tracks only); a channel stays with its track's id.  Returns
+        device tensors allocated once per Kt and reused: audio float32
+        [S][Kt][hop] (zeros for an invalid target), delays int32 [S][Kt][M]
+        (the codes, -1 invalid), active uint8 [S][Kt] and block_start int64 [1],
+        the absolute sample of audio[..., 0] = clock - hop - A; consecutive
+        hops' blocks abut.  Every stream is written, listed by the step or not."""
+        dev = self.loc.torch_device
+        if xy is not None:
+            if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
+                raise ValueError("xy must be float32 [S][Kt][2]")
+            if num_targets is not None and int(num_targets) != xy.shape[1]:
+                raise ValueError("num_targets differs from xy's Kt")
+            Kt = xy.shape[1]
+            if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.S,)):
+                raise ValueError("count must be int32 [S]")
+            for t in (xy, count):
+                if t is not None and (t.device != dev or not t.is_contiguous()):
+                    raise ValueError("xy and count must be contiguous on the localizer's device")
+        else:
+            if count is not None:
+                raise ValueError("count goes with xy; the track table's targets are chosen by min_status")
+            Kt = BEAM_MAX_TARGETS if num_targets is None else int(num_targets)
+        o = self._beams.get(Kt)
+        if o is None:
+            S, n, M = self.S, max(Kt, 0), self.loc.dims.M
+            o = {"audio": torch.zeros((S, n, self.hop), dtype=torch.float32, device=dev),
+                 "delays": torch.zeros((S, n, M), dtype=torch.int32, device=dev),
+                 "active": torch.zeros((S, n), dtype=torch.uint8, device=dev),
+                 "block_start": torch.zeros(1, dtype=torch.int64, device=dev)}
+            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+        s = BeamOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in BeamOutputs._fields_])
+        check(load().tdoa_stream_beam(self._h, None if count is None else C.c_void_p(count.data_ptr()),
+                                      None if xy is None else C.c_void_p(xy.data_ptr()), Kt, int(min_status),
+                                      C.byref(s), C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_beam")
+        self._beams[Kt] = o  # kept only once the library accepted the arguments
+        return o
 
     def est_ptr(self):
         """(device address, is_float) of the EMA state: int64 [S][P][K] (DIRECT)

@@ -691,6 +691,129 @@ int tdoa_stream_track(tdoa_stream *st, const tdoa_track_params *prm,
  * tdoa_stream_track.  Valid until tdoa_stream_destroy.  Host only;
  * TDOA_ERR_INVALID for a NULL argument. */
 int tdoa_stream_tracks_device(tdoa_stream *st, const tdoa_track **tracks, const int32_t **next_id);
+
+/* ---- Listening: a steered delay-and-sum beamformer per peak / per track ----
+ * Every layer above ends in coordinates.  This one returns the signal of a
+ * source at plane coordinates (u, v) -- as xy / xy_ls / tdoa_track.x, y report
+ * them -- by aligning the mics on that point with fractional delays and
+ * averaging them: the source adds coherently, the other sources and the
+ * uncorrelated noise do not (1/M in power for white noise).  The reference has
+ * no such layer.
+ *
+ * FIR table h[TDOA_BEAM_PHASES][2 * TDOA_BEAM_HALF], built on the host in
+ * double arithmetic (tdoa_beam_fir): tap k = -7..8 of phase q = 0..31 sits at
+ * h[q][k + 7] and is a Kaiser-windowed sinc at the fractional delay q/32,
+ *     x = k - q/32;  h[q][k] = sinc(x) * I0(8 sqrt(1 - (x/8)^2)) / I0(8)
+ * for |x| <= 8, else 0 (sinc(x) = sin(pi x) / (pi x), sinc(0) = 1; I0 the
+ * modified Bessel function of order 0); each phase is then divided by its sum
+ * over k, so that it sums to 1, and rounded to float.  Phase 0 is exactly the
+ * unit tap at k = 0.
+ *
+ * Latency and the largest delay, per geometry, on the host in double:
+ *     Dmax = ceil(max_{i<j} |mic_i - mic_j| * fs / c) + 1   samples
+ *     A    = Dmax + TDOA_BEAM_HALF
+ * (by the triangle inequality no target's inter-mic delay exceeds the mic
+ * separation; the + 1 covers the fp32 roundings below).  Output sample n needs
+ * the input up to n + A: the streaming form runs A samples behind the clock.
+ *
+ * Steering of a target (u, v).  All arithmetic is fp32, every operation rounded
+ * on its own (no fused multiply-add), division and square root IEEE -- the
+ * tracker's convention -- in the expression order of the lag LUT
+ * (vga_heatmap.h:48-93), with h = height_offset, hypot3(a, b, c) =
+ * sqrtf((a*a + b*b) + c*c):
+ *     k = h / hypot3(h, u, v)
+ *     xs = u*k;  ys = v*k;  zs = h*k             the point on the hemisphere
+ *     d_m = hypot3(zs, xs - mx_m, ys - my_m)      for every mic m
+ *     dmin = min_m d_m
+ *     t_m = ((d_m - dmin) / c) * (float)fs
+ *     r_m = floorf(t_m * 32.0f + 0.5f)
+ *     code_m = r_m >= 0 ? (r_m > 32 Dmax ? 32 Dmax : (int32)r_m) : 0   (a NaN r_m gives 0)
+ *     D_m = code_m >> 5;  q_m = code_m & 31
+ * The mic nearest to the point has code 0; a farther mic hears the source
+ * code_m / 32 samples later and is read that much ahead.  A target whose u or
+ * v is not finite is invalid, and so is target k >= count.
+ *
+ * Output of a valid target, with x_m[t] the samples' own values (u8 counts,
+ * int16 counts) as float, 0 for t < 0 and outside a block-form frame:
+ *     y[n] = (1/M) * sum_m sum_{k=-7..8} h[q_m][k] * x_m[n + D_m + k]
+ * accumulated in fp32 from 0, m ascending, then k ascending, one fused
+ * multiply-add per tap; the sum is multiplied by (1.0f / (float)M).  An invalid
+ * target's block is all zeros, its codes are -1, its active byte 0.  No DC
+ * removal, no gain control; u8 samples keep their offset (a constant 128 input
+ * gives 128).  The delays are constant within a block: interpolating the
+ * delays of a moving target inside a block is out of scope -- a block of a
+ * moving track is steered at the position the track table holds when the call
+ * runs, and the steering steps at block boundaries. */
+#define TDOA_BEAM_HALF 8
+#define TDOA_BEAM_PHASES 32
+#define TDOA_BEAM_MAX_TARGETS 8
+
+typedef struct tdoa_beam_geometry {  /* what steering reads of a context */
+    int32_t num_mics;        /* M, 2..TDOA_MAX_MICS */
+    int32_t sample_rate_hz;  /* fs > 0 */
+    float speed_of_sound;    /* c > 0, m/s */
+    float height_offset;     /* h > 0, m */
+    float mic_xy[TDOA_MAX_MICS][2];  /* metres; rows >= M are not read */
+} tdoa_beam_geometry;
+
+typedef struct tdoa_beam_outputs {   /* audio is required, the others may be NULL */
+    float *audio;            /* [rows][Kt][n]  n = frame_len (block form) or hop (streaming) */
+    int32_t *delays;         /* [rows][Kt][M]  the codes, -1 for an invalid target */
+    uint8_t *active;         /* [rows][Kt]     1 valid, 0 invalid */
+    int64_t *block_start;    /* [1] streaming only: the absolute sample of audio[.][.][0] */
+} tdoa_beam_outputs;
+
+/* The FIR table above, float [32][16].  Host only. */
+int tdoa_beam_fir(float *h);
+/* The geometry of the context a config would make: validates num_mics,
+ * sample_rate_hz, speed_of_sound, height_offset and mic_xy as tdoa_create does
+ * (NULL mic_xy with 3 mics: the reference triangle).  Host only, no device. */
+int tdoa_beam_geometry_of(const tdoa_config *cfg, tdoa_beam_geometry *g);
+/* A and Dmax of a geometry / of a context (either pointer may be NULL).
+ * TDOA_ERR_INVALID for a geometry outside the ranges above, a non-finite mic
+ * coordinate, or Dmax > 65536. */
+int tdoa_beam_latency_of(const tdoa_beam_geometry *g, int32_t *A, int32_t *Dmax);
+int tdoa_beam_latency(const tdoa_ctx *ctx, int32_t *A, int32_t *Dmax);
+int tdoa_get_beam_geometry(const tdoa_ctx *ctx, tdoa_beam_geometry *g);
+
+/* The block form (kernel k_beam, one workgroup per frame): frames is device
+ * int16 [B][M][N], the layout tdoa_localize_batch takes; count device [B] or
+ * NULL for all Kt; xy device [B][Kt][2]; outputs audio [B][Kt][N] for
+ * n in [0, N), delays [B][Kt][M], active [B][Kt] (block_start is not written).
+ * Asynchronous on `stream`, no allocation, no synchronisation.  B = 0 returns
+ * TDOA_OK without a launch.  TDOA_ERR_INVALID, with tdoa_last_error naming the
+ * cause, before any device call: a NULL ctx, frames, xy, out or out->audio; Kt
+ * outside 1..TDOA_BEAM_MAX_TARGETS; B < 0 or B >= 2^31; a workgroup's staging
+ * (M (N + Dmax + 15) + 512) * 4 bytes beyond 150 KiB. */
+int tdoa_beam_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count,
+                    const float *xy, int32_t Kt, const tdoa_beam_outputs *out, void *stream);
+/* The same on host pointers for frames of N samples, from the same inline
+ * steering and tap-sum functions (csrc/tdoa_beam_rule.h): no device, no HIP. */
+int tdoa_beam_host(const tdoa_beam_geometry *g, int32_t N, const int16_t *frames, int64_t B,
+                   const int32_t *count, const float *xy, int32_t Kt, const tdoa_beam_outputs *out);
+/* The streaming form (kernel k_beam_ring<uint8_t | int16_t>, one workgroup per
+ * stream), for every pipeline kind: one more asynchronous call after
+ * step -> peaks -> track, a plain launch stream-ordered after the step and
+ * before the producer overwrites the ring rows it reads.  With e = the device
+ * clock after the last step (read on the device), it reads samples
+ * [e - hop - A - 7, e) of every stream's ring (sample t at row t mod
+ * capture_len; t < 0 is zero) and writes, for ALL S streams indexed by stream
+ * (not by slot, and whether or not the step listed the stream), the block
+ * n in [e - hop - A, e - A): audio [S][Kt][hop], delays [S][Kt][M],
+ * active [S][Kt], block_start [1] = e - hop - A.  Consecutive hops' blocks abut.
+ * Targets: with xy != NULL, xy[s][k] (device [S][Kt][2]) for k < count[s]
+ * (device [S]; NULL: all Kt) -- the caller scatters a step's peaks by
+ * stream_id; with xy == NULL the pipeline's own track table, target k = slot k
+ * of stream s at (x, y), valid iff its status >= min_status, so a channel is a
+ * track slot and stays with its id (count is not read).
+ * TDOA_ERR_INVALID before any device call: a NULL st, out or out->audio; Kt
+ * outside 1..TDOA_BEAM_MAX_TARGETS; xy == NULL before the first
+ * tdoa_stream_track; capture_len < 2 hop + A + Dmax + 16 (the reach of a block
+ * plus one hop of margin for the producer); a workgroup's staging
+ * (M (hop + Dmax + 15) + 512) * 4 bytes beyond 150 KiB.  With no step since
+ * create / reset it returns TDOA_OK and launches nothing. */
+int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt,
+                     int32_t min_status, const tdoa_beam_outputs *out, void *stream);
 int tdoa_stream_destroy(tdoa_stream *st);
 
 const char *tdoa_last_error(void);

@@ -11,6 +11,7 @@
 #include "tdoa_beam_rule.h"
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
+#include "tdoa_sep_rule.h"
 #include "tdoa_tables.h"
 
 #include <hip/hip_runtime.h>
@@ -57,6 +58,11 @@ struct tdoa_ctx {
     tdoa_beam_geometry beam_g;
     int beam_dmax = 0;
     tdoa_devmem beam_fir;
+    // the null-steering beamformer (tdoa_sep_batch): the window and twiddles of
+    // its block length L (0: none; frame_len at creation where that is a block it
+    // takes, tdoa_sep_set_block chooses another)
+    tdoa_devmem sep_tab;
+    int sep_L = 0;
     tdoa_kparams kp;
 };
 
@@ -192,6 +198,21 @@ int upload_beam(tdoa_ctx *c)
     return TDOA_OK;
 }
 
+// the separator's block length and its table: L = frame_len at creation where
+// that is a block it takes (tdoa_sep_set_block chooses another)
+int upload_sep(tdoa_ctx *c, int L)
+{
+    std::vector<float> tab(tdoa_sep_table_floats(L));
+    if (const int rc = tdoa_sep_table(L, tab.data()))
+        return rc;
+    tdoa_devmem mem;
+    if (mem.upload(tab.data(), vbytes(tab)) != hipSuccess)
+        return tdoa_fail(TDOA_ERR_NOMEM, "uploading the separator's window and twiddles failed");
+    c->sep_tab = std::move(mem);  // (the table it held goes with mem)
+    c->sep_L = L;
+    return TDOA_OK;
+}
+
 // the kernel parameters: the tables' scalars, then every device pointer
 void wire_kparams(tdoa_ctx *c)
 {
@@ -253,6 +274,12 @@ extern "C" int tdoa_create(const tdoa_config *cfg, int device, tdoa_ctx **out)
         return rc;
     if (const int rc = upload_beam(c.get()))
         return rc;
+    // (asked without tdoa_sep_check: a frame_len the separator does not take is no error here)
+    const int N = c->t.N;
+    if (c->beam_dmax > 0 && N >= 128 && N <= 2048 && (N & (N - 1)) == 0 && N >= 8 * (int64_t)c->beam_dmax) {
+        if (const int rc = upload_sep(c.get(), N))
+            return rc;
+    }
     wire_kparams(c.get());
     *out = c.release();
     return TDOA_OK;
@@ -586,6 +613,57 @@ extern "C" int tdoa_beam_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, 
     HIP_TRY(hipSetDevice(ctx->device));
     return tdoa_launch_beam(g, Dmax, frames, true, 0, nullptr, B, ctx->t.N, count, xy, nullptr, 0, Kt, fir, *out,
                             stream);
+}
+
+extern "C" int tdoa_sep_set_block(tdoa_ctx *ctx, int32_t L)
+{
+    if (!ctx)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_set_block: NULL ctx");
+    tdoa_beam_geometry g;
+    int Dmax = 0;
+    const float *fir = nullptr;
+    if (const int rc = tdoa_ctx_beam(ctx, "tdoa_sep_set_block", &g, &Dmax, &fir))
+        return rc;
+    if (const int rc = tdoa_sep_check("tdoa_sep_set_block", Dmax, L, 1, TDOA_SEP_LOADING, ctx, ctx))
+        return rc;
+    if (L == ctx->sep_L)
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipDeviceSynchronize());  // launches in flight read the table this replaces
+    return upload_sep(ctx, L);
+}
+
+extern "C" int tdoa_sep_get_block(const tdoa_ctx *ctx, int32_t *L)
+{
+    if (!ctx || !L)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_get_block: NULL argument");
+    *L = ctx->sep_L;
+    return TDOA_OK;
+}
+
+extern "C" int tdoa_sep_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count, const float *xy,
+                              int32_t Kt, float loading, const tdoa_beam_outputs *out, void *stream)
+{
+    if (!ctx || !frames || !xy || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: NULL argument");
+    tdoa_beam_geometry g;
+    int Dmax = 0;
+    const float *fir = nullptr;
+    if (const int rc = tdoa_ctx_beam(ctx, "tdoa_sep_batch", &g, &Dmax, &fir))
+        return rc;
+    if (ctx->sep_L == 0)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: the context has no block length: frame_len %d is no "
+                                           "power of two in 128..2048 with L >= 8 Dmax = %d (tdoa_sep_set_block "
+                                           "chooses one)", ctx->t.N, 8 * Dmax);
+    if (const int rc = tdoa_sep_check("tdoa_sep_batch", Dmax, ctx->sep_L, Kt, loading, out, out->audio))
+        return rc;
+    if (B < 0 || B >= ((int64_t)1 << 31))
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: B %lld outside [0, 2^31)", (long long)B);
+    if (B == 0)
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return tdoa_launch_sep(g, Dmax, frames, true, 0, nullptr, B, ctx->sep_L, count, xy, nullptr, 0, Kt, loading,
+                           ctx->sep_tab.get<float>(), nullptr, *out, stream);
 }
 
 extern "C" int tdoa_localize_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B,

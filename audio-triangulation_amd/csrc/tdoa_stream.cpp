@@ -29,6 +29,7 @@
 #include "tdoa_beam_rule.h"
 #include "tdoa_devmem.h"
 #include "tdoa_internal.h"
+#include "tdoa_sep_rule.h"
 #include "tdoa_track_rule.h"
 
 // a step's outputs, either engine's: tdoa_stream_outputs with max_L null and
@@ -69,6 +70,9 @@ struct tdoa_stream {
     tdoa_devmem mem;  // one allocation for all state
     tdoa_devmem peak_lags;  // tdoa_stream_peaks: [S][TDOA_MAX_PEAKS][P] lag tuples when only the refinement reads them
     tdoa_devmem track_mem;  // tdoa_stream_track: tracks [S][TDOA_MAX_TRACKS], then next_id [S]
+    // tdoa_stream_sep: the window and twiddles of L = 2 hop, then the tails [S][4][hop]; made at its first call
+    tdoa_devmem sep_mem;
+    int32_t sep_kt = 0;     // ... the Kt of its last call: another Kt zeroes the tails
     int use_graph;
     int64_t hop = 0;  // steps enqueued since create / reset: the counter slot's parity
     step_graph g[2];  // one per counter parity; released before mem
@@ -430,6 +434,10 @@ extern "C" int tdoa_stream_reset(tdoa_stream *st, void *stream)
     HIP_TRY(hipMemsetAsync(st->mem.get<void>(), 0, st->mem.bytes(), (hipStream_t)stream));
     if (st->track_mem)  // no tracks, ids from 1 again
         HIP_TRY(hipMemsetAsync(st->track_mem.get<void>(), 0, st->track_mem.bytes(), (hipStream_t)stream));
+    if (st->sep_mem) {  // the tails behind the table
+        const size_t tab = tdoa_sep_table_floats(2 * st->sp.H) * sizeof(float);
+        HIP_TRY(hipMemsetAsync(st->sep_mem.get<char>() + tab, 0, st->sep_mem.bytes() - tab, (hipStream_t)stream));
+    }
     st->hop = 0;  // both counter slots are zero again
     return TDOA_OK;
 }
@@ -617,6 +625,55 @@ extern "C" int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const flo
     HIP_TRY(hipSetDevice(st->device));
     return tdoa_launch_beam(g, Dmax, st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S, hop, count, xy,
                             xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt, fir, *out, stream);
+}
+
+extern "C" int tdoa_stream_sep(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt, int32_t min_status,
+                               float loading, const tdoa_beam_outputs *out, void *stream)
+{
+    if (!st || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: NULL argument");
+    tdoa_beam_geometry g;
+    int Dmax = 0;
+    const float *fir = nullptr;
+    if (const int rc = tdoa_ctx_beam(st->ctx, "tdoa_stream_sep", &g, &Dmax, &fir))
+        return rc;
+    const int hop = st->sp.H, L = 2 * hop;
+    if (const int rc = tdoa_sep_check("tdoa_stream_sep", Dmax, L, Kt, loading, out, out->audio))
+        return rc;
+    if (!xy && !st->track_mem)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: no xy and no track table yet (tdoa_stream_track "
+                                           "makes it)");
+    // a block reaches L = 2 hop samples back from the clock; one more hop is the producer's margin
+    if (st->sp.capture_len < 3 * (int64_t)hop)
+        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: capture_len %lld < 3 hop = %lld",
+                         (long long)st->sp.capture_len, (long long)(3 * (int64_t)hop));
+    if (st->hop == 0)  // no step since creation or reset: the clock has not moved
+        return TDOA_OK;
+    HIP_TRY(hipSetDevice(st->device));
+    const size_t tab_floats = tdoa_sep_table_floats(L);
+    const size_t tail_bytes = (size_t)st->S * TDOA_SEP_MAX_TARGETS * hop * sizeof(float);
+    bool clear = Kt != st->sep_kt;
+    if (!st->sep_mem) {
+        std::unique_ptr<float[]> tab(new float[tab_floats]);
+        if (const int rc = tdoa_sep_table(L, tab.get()))
+            return rc;
+        if (st->sep_mem.alloc(tab_floats * sizeof(float) + tail_bytes) != hipSuccess)
+            return tdoa_fail(TDOA_ERR_NOMEM, "tdoa_stream_sep: %zu bytes of table and tail state",
+                             tab_floats * sizeof(float) + tail_bytes);
+        if (hipMemcpy(st->sep_mem.get<void>(), tab.get(), tab_floats * sizeof(float), hipMemcpyHostToDevice) !=
+            hipSuccess) {
+            st->sep_mem.release();
+            return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_sep: uploading the window and twiddles failed");
+        }
+        clear = true;
+    }
+    float *tail = st->sep_mem.get<float>() + tab_floats;
+    if (clear && hipMemsetAsync(tail, 0, tail_bytes, (hipStream_t)stream) != hipSuccess)
+        return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_sep: clearing the tails failed");
+    st->sep_kt = Kt;
+    return tdoa_launch_sep(g, Dmax, st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S, L, count, xy,
+                           xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt, loading,
+                           st->sep_mem.get<float>(), tail, *out, stream);
 }
 
 extern "C" int tdoa_stream_destroy(tdoa_stream *st)

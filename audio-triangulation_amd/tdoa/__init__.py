@@ -9,11 +9,12 @@ See include/tdoa.h for the C ABI and DESIGN.md for the kernels.
 from ._lib import (ENGINE_DIRECT, ENGINE_GCC_PHAT, EXPORTED_SYMBOLS, LIB_PATH,  # noqa: F401
                    MAX_TRACKS, TRACK_DEFAULTS, TRACK_FIELDS, TdoaError, Track, TrackOutputs, TrackParams,
                    BeamGeometry, BeamOutputs, band_weights, beam_fir, beam_geometry, beam_host, beam_latency,
-                   decay_us, dpss_q15, load, track_host, track_params)
+                   decay_us, dpss_q15, load, sep_check, sep_window, track_host, track_params,
+                   SEP_LOADING, SEP_MAX_TARGETS)
 
 __all__ = ["Localizer", "TdoaError", "load", "dpss_q15", "decay_us", "band_weights", "track_host", "track_params",
            "TrackParams", "TrackOutputs", "TRACK_DTYPE", "beam_fir", "beam_geometry", "beam_latency", "beam_host",
-           "BeamGeometry", "BeamOutputs"]
+           "BeamGeometry", "BeamOutputs", "sep_window", "sep_check", "SEP_LOADING", "SEP_MAX_TARGETS"]
 
 
 def __getattr__(name):

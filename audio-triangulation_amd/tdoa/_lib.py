@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "tdoa_track_batch", "tdoa_track_host", "tdoa_stream_track", "tdoa_stream_tracks_device",
     "tdoa_beam_fir", "tdoa_beam_geometry_of", "tdoa_beam_latency_of", "tdoa_beam_latency", "tdoa_get_beam_geometry",
     "tdoa_beam_batch", "tdoa_beam_host", "tdoa_stream_beam",
+    "tdoa_sep_window", "tdoa_sep_check_of", "tdoa_sep_set_block", "tdoa_sep_get_block", "tdoa_sep_batch", "tdoa_stream_sep",
     "tdoa_band_weights", "tdoa_set_bin_weights", "tdoa_set_band_hz", "tdoa_get_bin_weights",
     "tdoa_set_sample_format", "tdoa_get_sample_format",
     # tdoa_reference_abi.h
@@ -47,6 +48,9 @@ EXPORTED_SYMBOLS = [
     "tdoa_ref_set_clock", "tdoa_ref_set_device",
     "mic_a_location", "mic_b_location", "mic_c_location",
 ]
+
+SEP_MAX_TARGETS = 4   # TDOA_SEP_MAX_TARGETS
+SEP_LOADING = 1e-2    # TDOA_SEP_LOADING
 
 
 class TdoaError(RuntimeError):
@@ -251,6 +255,12 @@ def load() -> C.CDLL:
     L.tdoa_beam_batch.argtypes = [P, P, I64, P, P, I32, C.POINTER(BeamOutputs), P]
     L.tdoa_beam_host.argtypes = [C.POINTER(BeamGeometry), I32, P, I64, P, P, I32, C.POINTER(BeamOutputs)]
     L.tdoa_stream_beam.argtypes = [P, P, P, I32, I32, C.POINTER(BeamOutputs), P]
+    L.tdoa_sep_window.argtypes = [I32, P]
+    L.tdoa_sep_check_of.argtypes = [C.POINTER(BeamGeometry), I32, I32, C.c_float]
+    L.tdoa_sep_set_block.argtypes = [P, I32]
+    L.tdoa_sep_get_block.argtypes = [P, C.POINTER(I32)]
+    L.tdoa_sep_batch.argtypes = [P, P, I64, P, P, I32, C.c_float, C.POINTER(BeamOutputs), P]
+    L.tdoa_stream_sep.argtypes = [P, P, P, I32, I32, C.c_float, C.POINTER(BeamOutputs), P]
     L.tdoa_band_weights.argtypes = [I32, I32, C.c_double, C.c_double, C.c_double, P]
     L.tdoa_set_bin_weights.argtypes = [P, P]
     L.tdoa_set_band_hz.argtypes = [P, C.c_double, C.c_double, C.c_double]
@@ -419,3 +429,20 @@ def beam_host(geometry: BeamGeometry, frames, xy, count=None) -> dict:
     check(load().tdoa_beam_host(C.byref(geometry), N, ptr(frames), B, None if count is None else ptr(count), ptr(xy),
                                 Kt, C.byref(out)), "tdoa_beam_host")
     return o
+
+
+def sep_window(L: int):
+    """The separator's analysis / synthesis window (tdoa_sep_window): float32
+    [L], periodic sqrt-Hann, L a power of two in 128..2048.  Host only."""
+    import numpy as np
+    g = np.zeros(max(int(L), 1), np.float32)
+    check(load().tdoa_sep_window(int(L), g.ctypes.data_as(C.c_void_p)), "tdoa_sep_window")
+    return g
+
+
+def sep_check(geometry: BeamGeometry, L: int, num_targets: int = 1, loading: float = SEP_LOADING) -> None:
+    """Raises TdoaError unless a geometry, a block length L, a target count
+    and a loading make a block the separator takes (tdoa_sep_check_of: L a
+    power of two in 128..2048, L >= 8 Dmax, 1..4 targets, loading in
+    [1e-4, 1e4]).  Host only."""
+    check(load().tdoa_sep_check_of(C.byref(geometry), int(L), int(num_targets), float(loading)), "tdoa_sep_check_of")

@@ -78,6 +78,12 @@ explicit plane coordinates -- read from the capture rings behind the device
 clock, for every stream whether the step listed it or not, A = Dmax + 8
 samples behind the clock (Localizer.beam_latency()); consecutive blocks abut.
 
+sep() separates them (tdoa_stream_sep: k_sep; include/tdoa.h, "Separating"):
+the same targets, at most 4, but channel k nulls the stream's other valid
+targets -- a frequency-domain, diagonally loaded null-steering beamformer over
+half-overlapped blocks of L = 2 hop samples, overlap-added on the device; its
+audio runs L samples behind the clock.  It needs L >= 8 Dmax.
+
 mode="continuous" (a `gcc_phat` Localizer; tdoa_stream_create_continuous:
 k_stream_active in place of a trigger) chooses frames for continuous audio
 instead of clicks.  The ring is uint8 or int16 according to loc.sample_format.
@@ -96,8 +102,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import (BEAM_MAX_TARGETS, MAX_TRACKS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS, BeamOutputs, PeaksOutputs,
-                   PeaksParams, StreamOutputs, StreamOutputsF, TrackOutputs, check, load, track_params)
+from ._lib import (BEAM_MAX_TARGETS, MAX_TRACKS, SEP_LOADING, SEP_MAX_TARGETS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS,
+                   BeamOutputs, PeaksOutputs, PeaksParams, StreamOutputs, StreamOutputsF, TrackOutputs, check, load, track_params)
 from .localizer import Localizer
 
 
@@ -184,6 +190,7 @@ class StreamPipeline:
         self._tracks = {}  # (T, Kp) -> the output tensors of track()
         self._tracks_last = None
         self._beams = {}  # Kt -> the output tensors of beam()
+        self._seps = {}  # Kt -> the output tensors of sep()
 
     def step(self) -> dict:
         """One hop for every stream (asynchronous on self.stream)."""
@@ -384,6 +391,58 @@ class StreamPipeline:
                                       None if xy is None else C.c_void_p(xy.data_ptr()), Kt, int(min_status),
                                       C.byref(s), C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_beam")
         self._beams[Kt] = o  # kept only once the library accepted the arguments
+        return o
+
+    def sep(self, xy: torch.Tensor | None = None, count: torch.Tensor | None = None,
+            num_targets: int | None = None, min_status: int = 2, loading: float = SEP_LOADING) -> dict:
+        """One block of null-steered audio per stream and target
+        (tdoa_stream_sep, kernel k_sep; the rule is in include/tdoa.h,
+        "Separating"): channel k has unit gain on target k and nulls on the
+        stream's other valid targets.  Asynchronous on self.stream: call it once
+        per hop after step() -- and after peaks() / track() when it separates
+        their results -- before the producer overwrites the ring rows of the
+        last 2 hop samples.
+
+        Targets as beam() takes them, at most 4: xy float32 [S][Kt][2] with
+        count int32 [S], or -- xy None -- the track table's slots k <
+        num_targets (default 4), valid iff status >= min_status.  loading: the
+        diagonal loading delta in [1e-4, 1e4].  Returns device tensors
+        allocated once per Kt and reused: audio float32 [S][Kt][hop], the
+        overlap-added block whose first sample is block_start int64 [1] =
+        clock - 2 hop; delays int32 [S][Kt][M]; active uint8 [S][Kt].
+        Consecutive hops' blocks abut; a call with another Kt starts the
+        overlap-add afresh, and so does reset()."""
+        dev = self.loc.torch_device
+        if xy is not None:
+            if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
+                raise ValueError("xy must be float32 [S][Kt][2]")
+            if num_targets is not None and int(num_targets) != xy.shape[1]:
+                raise ValueError("num_targets differs from xy's Kt")
+            Kt = xy.shape[1]
+            if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.S,)):
+                raise ValueError("count must be int32 [S]")
+            for t in (xy, count):
+                if t is not None and (t.device != dev or not t.is_contiguous()):
+                    raise ValueError("xy and count must be contiguous on the localizer's device")
+        else:
+            if count is not None:
+                raise ValueError("count goes with xy; the track table's targets are chosen by min_status")
+            Kt = SEP_MAX_TARGETS if num_targets is None else int(num_targets)
+        o = self._seps.get(Kt)
+        if o is None:
+            S, n, M = self.S, max(Kt, 0), self.loc.dims.M
+            o = {"audio": torch.zeros((S, n, self.hop), dtype=torch.float32, device=dev),
+                 "delays": torch.zeros((S, n, M), dtype=torch.int32, device=dev),
+                 "active": torch.zeros((S, n), dtype=torch.uint8, device=dev),
+                 "block_start": torch.zeros(1, dtype=torch.int64, device=dev)}
+            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+        s = BeamOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in BeamOutputs._fields_])
+        check(load().tdoa_stream_sep(self._h, None if count is None else C.c_void_p(count.data_ptr()),
+                                     None if xy is None else C.c_void_p(xy.data_ptr()), Kt, int(min_status),
+                                     float(loading), C.byref(s), C.c_void_p(self.stream.cuda_stream)),
+              "tdoa_stream_sep")
+        self._seps[Kt] = o  # kept only once the library accepted the arguments
         return o
 
     def est_ptr(self):

@@ -814,6 +814,123 @@ int tdoa_beam_host(const tdoa_beam_geometry *g, int32_t N, const int16_t *frames
  * create / reset it returns TDOA_OK and launches nothing. */
 int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt,
                      int32_t min_status, const tdoa_beam_outputs *out, void *stream);
+
+/* ---- Separating: a null-steering beamformer, one channel per target ----
+ * The delay-and-sum above averages uncorrelated noise out; a second SOURCE it
+ * passes a few dB down at most, at low frequencies not down at all.  This
+ * layer uses the other targets' positions: per frequency bin a linearly
+ * constrained beamformer with unit gain on target j and nulls on the other
+ * valid targets of the same row, diagonally loaded so that it degrades to the
+ * delay-and-sum where the array cannot separate.  The reference has no such
+ * layer.
+ *
+ * Per row (a block-form frame, a stream), block length L (a power of two in
+ * 128..2048), M mics, Kt <= TDOA_SEP_MAX_TARGETS targets of which J are valid:
+ *
+ * 1. Steering.  code_{j,m} of target j and mic m is the delay-and-sum rule's
+ *    (beam_code, "Listening"), unchanged, and so is validity: finite (u, v),
+ *    k < count, or a track status >= min_status.  tau = code / 32 samples.
+ * 2. Analysis.  x_m[t] is the samples' own values as float (u8 keeps its
+ *    offset), 0 for t < 0.  Window: periodic sqrt-Hann,
+ *        g[n] = sqrt(0.5 - 0.5 cos(2 pi n / L)),   n = 0..L-1,
+ *    built on the host in double and rounded to float (tdoa_sep_window).
+ *        X_m[k] = sum_n (g[n] * x_m[n]) e^{-2 pi i k n / L},   k = 0..L/2
+ *    (the product in fp32; the transform an fp32 FFT).
+ * 3. Steering vectors.
+ *        p = (k * code_{j,m}) mod 32 L          in integers, before any float
+ *        a_{j,m}[k] = exp(-2 pi i p / (32 L))
+ * 4. Weights per bin.  A = [a_{j,m}] is M x J over the valid targets,
+ *        G = A^H A + delta M I                  delta = `loading`
+ *        W = (1 + delta) A G^-1
+ *        Y_j[k] = sum_m conj(W[m][j]) X_m[k]  =  (1 + delta) [G^-1 (A^H X)]_j
+ *    G is J x J Hermitian positive definite (its diagonal is M + delta M); it is
+ *    solved by Cholesky factorisation and two triangular solves, one bin per
+ *    thread, in registers.  The a_{j,m} and X_m are fp32 values; A^H A, A^H X
+ *    and the solve are accumulated in double from them, because a pivot of G
+ *    is delta M left of (1 + delta) M minus nearly as much -- in fp32 the bins
+ *    the array cannot separate (the lowest ones, a u8 ring's offset among
+ *    them) would lose 1 / delta of their precision.  Y_j is rounded to fp32.
+ *    An invalid target takes part as a zero
+ *    column: its row of G is delta M on the diagonal and 0 elsewhere, which
+ *    leaves the valid targets' solution what the J x J system gives.
+ *    With J = 1: G = M (1 + delta), Y = (1/M) sum_m conj(a_m) X_m, exactly the
+ *    frequency-domain delay-and-sum.  With G0 = A^H A, the response of channel
+ *    j to a source at target i's steering vector is
+ *        [(1 + delta) (G0 + delta M I)^-1 G0]_ji :
+ *    on the own target (i = j) it is 1 - O(delta) where G0 is well conditioned
+ *    and exactly 1 for J = 1; on another target it is O(delta M / lambda_min(G0))
+ *    -- a null as deep as the loading allows.  As delta -> infinity,
+ *    (1 + delta) (G0 + delta M I)^-1 -> I / M: every channel tends to its
+ *    delay-and-sum.  loading is a float in [1e-4, 1e4]; TDOA_SEP_LOADING is the
+ *    default.
+ * 5. Synthesis.  y_j[n] = g[n] * irfft(Y_j)[n], irfft the inverse real
+ *    transform of length L including its 1/L (the imaginary parts of bins 0
+ *    and L/2 are not read).  An invalid target's block is zeros, its codes are
+ *    -1, its active byte 0.
+ * 6. Circular-delay guard.  The delays act circularly within a block, so the
+ *    block must be long against them: TDOA_ERR_INVALID unless L >= 8 Dmax
+ *    (Dmax as tdoa_beam_latency reports it) and L is a power of two in
+ *    128..2048.
+ * g[n]^2 + g[n + L/2]^2 = 1: blocks at 50 % overlap add up to the full
+ * reconstruction.  Steering is constant within a block, as above. */
+#define TDOA_SEP_MAX_TARGETS 4
+#define TDOA_SEP_LOADING 1e-2f
+#define TDOA_SEP_LOADING_MIN 1e-4f
+#define TDOA_SEP_LOADING_MAX 1e4f
+
+/* g[0..L) above, float [L].  Host only.  TDOA_ERR_INVALID for a NULL g or an L
+ * that is no power of two in 128..2048. */
+int tdoa_sep_window(int32_t L, float *g);
+/* The argument rules of both forms on the host, no device: TDOA_OK if a
+ * geometry's Dmax, L, Kt and loading are a block the separator takes,
+ * TDOA_ERR_INVALID with tdoa_last_error naming the cause otherwise. */
+int tdoa_sep_check_of(const tdoa_beam_geometry *g, int32_t L, int32_t Kt, float loading);
+
+/* The block form's block length L of a context: frame_len at creation where
+ * that is a block the separator takes (a power of two in 128..2048 with
+ * L >= 8 Dmax), else none (0).  tdoa_sep_set_block chooses another -- a context
+ * whose frame_len is 1024 separates blocks of 128 -- and uploads its window and
+ * twiddles: it allocates and synchronises the device, so it is a setup call,
+ * not a per-block one.  TDOA_ERR_INVALID for a NULL ctx or an L step 6 refuses
+ * (the block length in force stays). */
+int tdoa_sep_set_block(tdoa_ctx *ctx, int32_t L);
+int tdoa_sep_get_block(const tdoa_ctx *ctx, int32_t *L);
+/* The block form (kernel k_sep, one workgroup per frame), the stateless core:
+ * one STFT block per row of the context's block length L (tdoa_sep_get_block;
+ * the kernel reads nothing else of frame_len).  frames is device int16 [B][M][L];
+ * count device [B] or NULL for all Kt; xy device [B][Kt][2]; outputs
+ * audio [B][Kt][L] -- the synthesis-windowed block y_j, which the caller
+ * overlap-adds --, delays [B][Kt][M], active [B][Kt] (block_start is not
+ * written).  Asynchronous on `stream`, no allocation, no synchronisation.
+ * B = 0 returns TDOA_OK without a launch.  TDOA_ERR_INVALID, with
+ * tdoa_last_error naming the cause, before any device call: a NULL ctx, frames,
+ * xy, out or out->audio; Kt outside 1..TDOA_SEP_MAX_TARGETS; B < 0 or
+ * B >= 2^31; loading outside [1e-4, 1e4] or not finite; a context without a
+ * block length. */
+int tdoa_sep_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count, const float *xy,
+                   int32_t Kt, float loading, const tdoa_beam_outputs *out, void *stream);
+/* The streaming form (kernel k_sep over the capture rings, uint8 or int16, one
+ * workgroup per stream), for every pipeline kind: one more plain launch after
+ * step -> peaks -> track.  L = 2 hop.  With e = the device clock after the last
+ * step (read on the device), it reads samples [e - L, e) of every stream's
+ * ring (t < 0 is zero), adds the first half of each target's block y_j to the
+ * stream's saved tail and writes that as the block n in [e - L, e - hop):
+ * audio [S][Kt][hop], delays [S][Kt][M], active [S][Kt], block_start [1] =
+ * e - L; the second half is the new tail.  Consecutive hops' blocks abut and
+ * add up to the full reconstruction, L samples behind the clock.  Targets as
+ * tdoa_stream_beam takes them: xy [S][Kt][2] with count [S], or -- xy NULL --
+ * the pipeline's own track table, channel k = slot k, valid iff its status >=
+ * min_status.  The tail state, float [S][TDOA_SEP_MAX_TARGETS][hop], and the
+ * window are allocated at the first call; the tails are zeroed then, by
+ * tdoa_stream_reset, and by a call whose Kt differs from the call's before.
+ * With no step since create / reset it returns TDOA_OK and launches nothing.
+ * TDOA_ERR_INVALID before any device call: a NULL st, out or out->audio; Kt
+ * outside 1..TDOA_SEP_MAX_TARGETS; xy == NULL before the first
+ * tdoa_stream_track; loading outside its range; the L conditions of step 6 on
+ * L = 2 hop; capture_len < 3 hop (the block plus one hop of margin for the
+ * producer). */
+int tdoa_stream_sep(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt, int32_t min_status,
+                    float loading, const tdoa_beam_outputs *out, void *stream);
 int tdoa_stream_destroy(tdoa_stream *st);
 
 const char *tdoa_last_error(void);

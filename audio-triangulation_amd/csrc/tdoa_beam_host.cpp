@@ -48,13 +48,20 @@ size_t tdoa_beam_lds(int M, int n, int Dmax)
     return (rows + TDOA_BEAM_PHASES * TDOA_BEAM_TAPS) * sizeof(float);
 }
 
-int tdoa_beam_check(const char *fn, const tdoa_beam_geometry &g, int Dmax, int n, int32_t Kt, const void *out,
-                    const void *audio, bool device)
+int tdoa_beam_check_outputs(const char *fn, int32_t Kt, int Kt_max, const void *out, const void *audio)
 {
     if (!out || !audio)
         return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument (outputs.audio is required)", fn);
-    if (Kt < 1 || Kt > TDOA_BEAM_MAX_TARGETS)
-        return tdoa_fail(TDOA_ERR_INVALID, "%s: Kt %d outside 1..%d", fn, (int)Kt, TDOA_BEAM_MAX_TARGETS);
+    if (Kt < 1 || Kt > Kt_max)
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: Kt %d outside 1..%d", fn, (int)Kt, Kt_max);
+    return TDOA_OK;
+}
+
+int tdoa_beam_check(const char *fn, const tdoa_beam_geometry &g, int Dmax, int n, int32_t Kt, const void *out,
+                    const void *audio, bool device)
+{
+    if (const int rc = tdoa_beam_check_outputs(fn, Kt, TDOA_BEAM_MAX_TARGETS, out, audio))
+        return rc;
     if (n < 1)
         return tdoa_fail(TDOA_ERR_INVALID, "%s: block length %d < 1", fn, n);
     const size_t lds = tdoa_beam_lds(g.num_mics, n, Dmax);
@@ -91,6 +98,7 @@ extern "C" int tdoa_beam_host(const tdoa_beam_geometry *g, int32_t N, const int1
     if (B < 0 || B >= ((int64_t)1 << 31))
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_host: B %lld outside [0, 2^31)", (long long)B);
     const int M = g->num_mics;
+    const tdoa_beam_targets targets{count, xy, nullptr, 0, Kt};
     float fir[TDOA_BEAM_PHASES][TDOA_BEAM_TAPS];
     tdoa_beam_fir(&fir[0][0]);
     // row m: x_m[t] at index t + 7, zero outside [0, N)
@@ -101,11 +109,10 @@ extern "C" int tdoa_beam_host(const tdoa_beam_geometry *g, int32_t N, const int1
         for (int m = 0; m < M; m++)
             for (int t = 0; t < N; t++)
                 xs[m * L + t + (TDOA_BEAM_HALF - 1)] = (float)frames[((size_t)b * M + m) * N + t];
-        const int cnt = count ? count[b] : Kt;
         for (int k = 0; k < Kt; k++) {
             const size_t row = (size_t)b * Kt + k;
-            const float u = xy[row * 2], v = xy[row * 2 + 1];
-            const bool valid = k < cnt && beam_finite(u) && beam_finite(v);
+            float u, v;
+            const bool valid = beam_target(targets, b, k, Kt, &u, &v);
             int32_t code[TDOA_MAX_MICS];
             for (int m = 0; m < M; m++)
                 code[m] = valid ? beam_code(*g, Dmax, u, v, m) : -1;

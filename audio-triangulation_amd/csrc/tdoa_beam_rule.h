@@ -4,8 +4,11 @@
 // steering of a target to its per-mic delay codes and the 16-tap sum of one
 // mic.  Every float operation of the steering is written on its own and
 // contraction is off inside it whatever the TU's flags; the tap sum is one
-// fused multiply-add per tap on both sides.  No HIP header: a plain host
-// compiler reads it.
+// fused multiply-add per tap on both sides.  Also what a launch of either
+// beamformer (k_sep too, tdoa_sep.hip) reads and steers at, tdoa_beam_source
+// and tdoa_beam_targets, and the rule that makes a target valid (beam_target).
+// No HIP header: a plain host compiler reads it; the device code the kernels
+// share is in tdoa_beam_dev.h.
 #pragma once
 
 #include <stddef.h>
@@ -98,16 +101,50 @@ TDOA_BEAM_HD float beam_scale(float acc, int M)
     return acc * inv;
 }
 
-// the launcher of k_beam / k_beam_ring (tdoa_beam.hip): one workgroup per row,
-// blocks of n outputs.  A ring launch (pos set) reads T [rows][capture_len][M]
+// a launch's input.  A ring launch (pos set) reads T [rows][capture_len][M]
 // samples at `src` (T = int16_t for pcm16, else uint8_t) behind the device clock
-// *pos; a block launch reads int16 [rows][M][n].  Targets: xy [rows][Kt][2] with
-// count [rows] (null: all), or -- xy null -- slot k of tracks [rows][8], valid
-// iff status >= min_status.  fir: the device copy of tdoa_beam_fir's table.
-int tdoa_launch_beam(const tdoa_beam_geometry &g, int Dmax, const void *src, bool pcm16, int64_t capture_len,
-                     const int64_t *pos, int64_t rows, int n, const int32_t *count, const float *xy,
-                     const tdoa_track *tracks, int32_t min_status, int32_t Kt, const float *fir,
-                     const tdoa_beam_outputs &out, void *stream);
+// *pos; a block launch (pos null) reads int16 [rows][M][n] frames.
+struct tdoa_beam_source {
+    const void *src;
+    bool pcm16;
+    int64_t capture_len;  // ring: samples per stream
+    const int64_t *pos;   // ring: the device clock (samples consumed)
+    int64_t rows;         // streams, frames
+};
+
+// a launch's targets: xy [rows][Kt][2] with count [rows] (null: all Kt), or --
+// xy null -- slot k of tracks [rows][TDOA_MAX_TRACKS], valid iff its status >=
+// min_status
+struct tdoa_beam_targets {
+    const int32_t *count;
+    const float *xy;
+    const tdoa_track *tracks;
+    int32_t min_status, Kt;
+};
+
+// target k (< Kt) of a row: its plane coordinates, and whether it is valid --
+// listed (k < count, or the slot's status) and finite
+TDOA_BEAM_HD bool beam_target(const tdoa_beam_targets &t, int64_t row, int k, int Kt, float *u, float *v)
+{
+    bool listed;
+    if (t.xy) {
+        const float *p = t.xy + (row * Kt + k) * 2;
+        *u = p[0];
+        *v = p[1];
+        listed = k < (t.count ? t.count[row] : Kt);
+    } else {
+        const tdoa_track *tr = t.tracks + row * TDOA_MAX_TRACKS + k;
+        *u = tr->x;
+        *v = tr->y;
+        listed = tr->status >= t.min_status;
+    }
+    return listed && beam_finite(*u) && beam_finite(*v);
+}
+
+// the launcher of k_beam / k_beam_ring (tdoa_beam.hip): one workgroup per row,
+// blocks of n outputs.  fir: the device copy of tdoa_beam_fir's table.
+int tdoa_launch_beam(const tdoa_beam_geometry &g, int Dmax, const tdoa_beam_source &source, int n,
+                     const tdoa_beam_targets &targets, const float *fir, const tdoa_beam_outputs &out, void *stream);
 
 // a context's geometry, largest delay and device FIR table (tdoa_capi.cpp);
 // TDOA_ERR_INVALID with the cause stored for a geometry the beamformer refuses
@@ -117,5 +154,7 @@ int tdoa_ctx_beam(const tdoa_ctx *c, const char *fn, tdoa_beam_geometry *g, int 
 // what the entry points share (tdoa_beam_host.cpp; host only)
 int tdoa_beam_dmax(const tdoa_beam_geometry &g, int *Dmax);  // validates g too
 size_t tdoa_beam_lds(int M, int n, int Dmax);     // a workgroup's dynamic LDS for blocks of n outputs
+// out and audio not null, Kt in 1..Kt_max: how tdoa_beam_check and tdoa_sep_check open
+int tdoa_beam_check_outputs(const char *fn, int32_t Kt, int Kt_max, const void *out, const void *audio);
 int tdoa_beam_check(const char *fn, const tdoa_beam_geometry &g, int Dmax, int n, int32_t Kt, const void *out,
                     const void *audio, bool device /* the LDS limit applies */);

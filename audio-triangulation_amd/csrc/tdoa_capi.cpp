@@ -594,25 +594,45 @@ extern "C" int tdoa_get_beam_geometry(const tdoa_ctx *ctx, tdoa_beam_geometry *g
     return TDOA_OK;
 }
 
+// What tdoa_beam_batch and tdoa_sep_batch share, before and after their own
+// argument checks: the context's beamformer geometry ...
+static int batch_beam_open(tdoa_ctx *ctx, const char *fn, const int16_t *frames, const float *xy,
+                           const tdoa_beam_outputs *out, tdoa_beam_geometry *g, int *Dmax, const float **fir)
+{
+    if (!ctx || !frames || !xy || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument", fn);
+    return tdoa_ctx_beam(ctx, fn, g, Dmax, fir);
+}
+
+// ... and the batch of B frames as a launch's source, the caller's xy as its targets
+static int batch_beam_io(const char *fn, const int16_t *frames, int64_t B, const int32_t *count, const float *xy,
+                         int32_t Kt, tdoa_beam_source *source, tdoa_beam_targets *targets)
+{
+    if (B < 0 || B >= ((int64_t)1 << 31))
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: B %lld outside [0, 2^31)", fn, (long long)B);
+    *source = tdoa_beam_source{frames, true, 0, nullptr, B};
+    *targets = tdoa_beam_targets{count, xy, nullptr, 0, Kt};
+    return TDOA_OK;
+}
+
 extern "C" int tdoa_beam_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count,
                                const float *xy, int32_t Kt, const tdoa_beam_outputs *out, void *stream)
 {
-    if (!ctx || !frames || !xy || !out)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_batch: NULL argument");
     tdoa_beam_geometry g;
     int Dmax = 0;
     const float *fir = nullptr;
-    if (const int rc = tdoa_ctx_beam(ctx, "tdoa_beam_batch", &g, &Dmax, &fir))
+    tdoa_beam_source source;
+    tdoa_beam_targets targets;
+    if (const int rc = batch_beam_open(ctx, "tdoa_beam_batch", frames, xy, out, &g, &Dmax, &fir))
         return rc;
     if (const int rc = tdoa_beam_check("tdoa_beam_batch", g, Dmax, ctx->t.N, Kt, out, out->audio, true))
         return rc;
-    if (B < 0 || B >= ((int64_t)1 << 31))
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_beam_batch: B %lld outside [0, 2^31)", (long long)B);
+    if (const int rc = batch_beam_io("tdoa_beam_batch", frames, B, count, xy, Kt, &source, &targets))
+        return rc;
     if (B == 0)
         return TDOA_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    return tdoa_launch_beam(g, Dmax, frames, true, 0, nullptr, B, ctx->t.N, count, xy, nullptr, 0, Kt, fir, *out,
-                            stream);
+    return tdoa_launch_beam(g, Dmax, source, ctx->t.N, targets, fir, *out, stream);
 }
 
 extern "C" int tdoa_sep_set_block(tdoa_ctx *ctx, int32_t L)
@@ -644,12 +664,12 @@ extern "C" int tdoa_sep_get_block(const tdoa_ctx *ctx, int32_t *L)
 extern "C" int tdoa_sep_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, const int32_t *count, const float *xy,
                               int32_t Kt, float loading, const tdoa_beam_outputs *out, void *stream)
 {
-    if (!ctx || !frames || !xy || !out)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: NULL argument");
     tdoa_beam_geometry g;
     int Dmax = 0;
     const float *fir = nullptr;
-    if (const int rc = tdoa_ctx_beam(ctx, "tdoa_sep_batch", &g, &Dmax, &fir))
+    tdoa_beam_source source;
+    tdoa_beam_targets targets;
+    if (const int rc = batch_beam_open(ctx, "tdoa_sep_batch", frames, xy, out, &g, &Dmax, &fir))
         return rc;
     if (ctx->sep_L == 0)
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: the context has no block length: frame_len %d is no "
@@ -657,13 +677,13 @@ extern "C" int tdoa_sep_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B, c
                                            "chooses one)", ctx->t.N, 8 * Dmax);
     if (const int rc = tdoa_sep_check("tdoa_sep_batch", Dmax, ctx->sep_L, Kt, loading, out, out->audio))
         return rc;
-    if (B < 0 || B >= ((int64_t)1 << 31))
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_sep_batch: B %lld outside [0, 2^31)", (long long)B);
+    if (const int rc = batch_beam_io("tdoa_sep_batch", frames, B, count, xy, Kt, &source, &targets))
+        return rc;
     if (B == 0)
         return TDOA_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    return tdoa_launch_sep(g, Dmax, frames, true, 0, nullptr, B, ctx->sep_L, count, xy, nullptr, 0, Kt, loading,
-                           ctx->sep_tab.get<float>(), nullptr, *out, stream);
+    return tdoa_launch_sep(g, Dmax, source, ctx->sep_L, targets, loading, ctx->sep_tab.get<float>(), nullptr, *out,
+                           stream);
 }
 
 extern "C" int tdoa_localize_batch(tdoa_ctx *ctx, const int16_t *frames, int64_t B,

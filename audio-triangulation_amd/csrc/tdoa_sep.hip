@@ -9,12 +9,10 @@
 // max(ceil(M/2), ceil(KT/2)) complex buffers of L points:
 //   1. the row's M x L samples, times the window, go to LDS two mics to a
 //      complex buffer, z_p[n] = g[n] x_{2p}[n] + i g[n] x_{2p+1}[n].  A ring's
-//      run is L M contiguous elements modulo the ring's capture_len M, fetched
-//      as k_beam_ring fetches it: 16-byte vectors where the address is 16-byte
-//      aligned and the vector lies inside the ring, element loads for the head,
-//      the tail and a vector at a wrap seam.  Samples before the stream's
-//      start are staged as zeros.
-//   2. thread (k, m) of the first wave steers target k to mic m's delay code.
+//      run is fetched by ring_stage (tdoa_beam_dev.h, shared with k_beam_ring),
+//      which says how.
+//   2. thread (k, m) of the first wave steers target k to mic m's delay code
+//      (beam_steer, in the same header).
 //   3. one forward FFT_L per mic pair, in place.
 //   4. thread k owns bins k and L - k of every buffer: it splits the pairs'
 //      transforms into X_m[k], accumulates b = A^H X and the lower triangle of
@@ -30,13 +28,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tdoa_beam_dev.h"
 #include "tdoa_internal.h"
 #include "tdoa_phat_lds.h"
 #include "tdoa_sep_rule.h"
 
 namespace {
 
-constexpr int SEP_GEO_WORDS = sizeof(tdoa_beam_geometry) / 4;
 constexpr int SEP_HEAD_BYTES = 256;  // geometry (80), codes [4][8] (128), validity [4] (16), padded
 
 static_assert(sizeof(tdoa_beam_geometry) + TDOA_SEP_MAX_TARGETS * (TDOA_MAX_MICS + 1) * 4 <= SEP_HEAD_BYTES,
@@ -44,20 +42,13 @@ static_assert(sizeof(tdoa_beam_geometry) + TDOA_SEP_MAX_TARGETS * (TDOA_MAX_MICS
 
 struct sep_kargs {
     tdoa_beam_geometry g;
-    const void *src;           // ring: T [rows][cl][M]; block: int16 [rows][M][L]
-    int64_t cl;                // ring: samples per stream
-    const int64_t *pos;        // ring: the device clock (samples consumed)
-    const int32_t *count;      // [rows], or null: all Kt
-    const float *xy;           // [rows][Kt][2], or null:
-    const tdoa_track *tracks;  // ... [rows][TDOA_MAX_TRACKS], target k = slot k
-    const float *tab;          // window [L], twiddles [2 L]
-    float *tail;               // ring: [rows][TDOA_SEP_MAX_TARGETS][L/2]
-    float *audio;              // ring: [rows][Kt][L/2]; block: [rows][Kt][L]
-    int32_t *delays;           // [rows][Kt][M]
-    uint8_t *active;           // [rows][Kt]
-    int64_t *block_start;      // [1]
+    tdoa_beam_source in;    // ring: T [rows][capture_len][M]; block: int16 [rows][M][L]
+    tdoa_beam_targets tg;
+    const float *tab;       // window [L], twiddles [2 L]
+    float *tail;            // ring: [rows][TDOA_SEP_MAX_TARGETS][L/2]
+    tdoa_beam_outputs out;  // audio: ring [rows][Kt][L/2], block [rows][Kt][L]; delays, active, block_start
     float loading;
-    int32_t Dmax, L, min_status;
+    int32_t Dmax, L;
 };
 
 // where sample l of mic m is staged: mic pair m / 2's buffer, real or imaginary part
@@ -74,7 +65,7 @@ struct frame_loader {
     // frame sample n of mic m is frames[row][m][n]
     static __device__ __forceinline__ void stage(const sep_kargs &a, float *zf, int64_t row, int64_t, int L, int M)
     {
-        const int16_t *fr = static_cast<const int16_t *>(a.src) + (size_t)row * M * L;
+        const int16_t *fr = static_cast<const int16_t *>(a.in.src) + (size_t)row * M * L;
         for (int i = threadIdx.x; i < M * L; i += TPB) {
             const int m = i / L, l = i - m * L;
             stage_put(zf, L, M, m, l, a.tab[l] * (float)fr[i]);
@@ -82,65 +73,23 @@ struct frame_loader {
     }
 };
 
-// element v of a 16-byte vector of T
-template <typename T> __device__ __forceinline__ float sep_vec_elem(const uint4 &x, int v)
-{
-    const uint32_t w[4] = {x.x, x.y, x.z, x.w};
-    if constexpr (sizeof(T) == 1)
-        return (float)((w[v >> 2] >> (8 * (v & 3))) & 0xFFu);
-    else
-        return (float)(int16_t)(w[v >> 1] >> (16 * (v & 1)));
-}
+// ring_stage's sample l of mic m, times the window (finite and not negative: a
+// zeroed sample stays +0), to its place
+struct sep_sink {
+    float *zf;
+    const float *win;
+    int L, M;
+    __device__ __attribute__((always_inline)) void operator()(int m, int l, float x) const
+    {
+        stage_put(zf, L, M, m, l, win[l] * x);
+    }
+};
 
 template <typename T> struct ring_loader {
     static constexpr bool RING = true;
-    // run element i (< L M) is sample tl + i / M of mic i % M
     static __device__ __forceinline__ void stage(const sep_kargs &a, float *zf, int64_t row, int64_t tl, int L, int M)
     {
-        constexpr int V = 16 / sizeof(T);
-        const int64_t cl = a.cl, R = cl * M;
-        const T *ring = static_cast<const T *>(a.src) + (size_t)row * R;
-        int64_t j0 = tl % cl;
-        if (j0 < 0)
-            j0 += cl;  // (rows of samples before the start are read, inside the ring, and zeroed below)
-        const int64_t b0 = j0 * M;  // < R; b0 + tot < 2 R: L <= cl
-        const int tot = L * M;
-        const int nz = tl < 0 ? (tl < -(int64_t)L ? L : (int)-tl) : 0;  // samples before the stream's start
-        // vector j covers run elements [head + (j - 1) V, head + j V): j = 0 is the partial head
-        const int head = (int)((V - (int)(((uintptr_t)(ring + b0) / sizeof(T)) % V)) % V);
-        const int NV = (tot - head + V - 1) / V + 1;
-        for (int j = threadIdx.x; j < NV; j += TPB) {
-            const int i0 = head + (j - 1) * V;
-            int64_t r = b0 + i0;
-            if (r >= R)
-                r -= R;
-            const bool whole = i0 >= 0 && i0 + V <= tot && r + V <= R && ((uintptr_t)(ring + r) & 15u) == 0;
-            uint4 x = {0u, 0u, 0u, 0u};
-            if (whole)
-                x = *reinterpret_cast<const uint4 *>(ring + r);
-            const int ia = i0 < 0 ? 0 : i0;
-            int l = ia / M, m = ia - l * M;
-#pragma unroll
-            for (int v = 0; v < V; v++) {
-                const int i = i0 + v;
-                if (i < 0 || i >= tot)
-                    continue;
-                float f;
-                if (whole) {
-                    f = sep_vec_elem<T>(x, v);
-                } else {
-                    int64_t e = b0 + i;  // in [0, 2 R)
-                    if (e >= R)
-                        e -= R;
-                    f = (float)ring[e];
-                }
-                stage_put(zf, L, M, m, l, l < nz ? 0.0f : a.tab[l] * f);
-                if (++m == M) {
-                    m = 0;
-                    l++;
-                }
-            }
-        }
+        ring_stage<T, TPB>(a.in.src, a.in.capture_len, row, tl, L, M, sep_sink{zf, a.tab, L, M});
     }
 };
 
@@ -211,48 +160,19 @@ template <typename Loader, int KT> __global__ void __launch_bounds__(TPB) k_sep(
     const float *win = a.tab, *tw = a.tab + L;
     const int64_t row = blockIdx.x;
 
-    if (tid < SEP_GEO_WORDS)
-        reinterpret_cast<uint32_t *>(&sg)[tid] = reinterpret_cast<const uint32_t *>(&a.g)[tid];
+    beam_geometry_to_lds(&sg, a.g);
     // step 1
     int64_t tl = 0;
     if constexpr (Loader::RING) {
-        tl = *a.pos - L;  // the position after the last step, less the block
-        if (row == 0 && tid == 0 && a.block_start)
-            *a.block_start = tl;
+        tl = *a.in.pos - L;  // the position after the last step, less the block
+        if (row == 0 && tid == 0 && a.out.block_start)
+            *a.out.block_start = tl;
     }
     Loader::stage(a, reinterpret_cast<float *>(zb), row, tl, L, M);
     __syncthreads();
 
     // step 2 (the FFT's barriers publish it)
-    if (tid < KT * TDOA_MAX_MICS) {
-        const int kt = tid >> 3, m = tid & 7;
-        const int64_t tg = row * KT + kt;
-        float u, v;
-        bool valid;
-        if (a.xy) {
-            const int cnt = a.count ? a.count[row] : KT;
-            u = a.xy[tg * 2];
-            v = a.xy[tg * 2 + 1];
-            valid = kt < cnt;
-        } else {
-            const tdoa_track *tr = a.tracks + row * TDOA_MAX_TRACKS + kt;
-            u = tr->x;
-            v = tr->y;
-            valid = tr->status >= a.min_status;
-        }
-        valid = valid && beam_finite(u) && beam_finite(v);
-        if (m < M) {
-            const int32_t code = valid ? beam_code(sg, Dmax, u, v, m) : -1;
-            s_code[kt][m] = code;
-            if (a.delays)
-                a.delays[tg * M + m] = code;
-        }
-        if (m == 0) {
-            s_valid[kt] = valid ? 1 : 0;
-            if (a.active)
-                a.active[tg] = valid ? 1 : 0;
-        }
-    }
+    beam_steer(a.tg, sg, Dmax, row, KT, M, s_code, s_valid, a.out.delays, a.out.active);
 
     // step 3
     const int NP = (M + 1) >> 1;
@@ -329,14 +249,14 @@ template <typename Loader, int KT> __global__ void __launch_bounds__(TPB) k_sep(
             const float y0 = on ? win[n] * (((j & 1) ? lo.y : lo.x) * invL) : 0.0f;
             const float y1 = on ? win[n + hop] * (((j & 1) ? hi.y : hi.x) * invL) : 0.0f;
             float *t = a.tail + ((size_t)row * TDOA_SEP_MAX_TARGETS + j) * hop + n;
-            a.audio[((size_t)row * KT + j) * hop + n] = *t + y0;
+            a.out.audio[((size_t)row * KT + j) * hop + n] = *t + y0;
             *t = y1;
         }
     } else {
         for (int i = tid; i < KT * L; i += TPB) {
             const int j = i / L, n = i - j * L;
             const f2 z = zb[(j >> 1) * L + n];
-            a.audio[((size_t)row * KT + j) * L + n] = s_valid[j] ? win[n] * (((j & 1) ? z.y : z.x) * invL) : 0.0f;
+            a.out.audio[((size_t)row * KT + j) * L + n] = s_valid[j] ? win[n] * (((j & 1) ? z.y : z.x) * invL) : 0.0f;
         }
     }
 }
@@ -370,37 +290,21 @@ template <typename Loader> int launch_kt(const sep_kargs &a, int64_t rows, int K
 
 }  // namespace
 
-int tdoa_launch_sep(const tdoa_beam_geometry &g, int Dmax, const void *src, bool pcm16, int64_t capture_len,
-                    const int64_t *pos, int64_t rows, int L, const int32_t *count, const float *xy,
-                    const tdoa_track *tracks, int32_t min_status, int32_t Kt, float loading, const float *tab,
-                    float *tail, const tdoa_beam_outputs &out, void *stream)
+int tdoa_launch_sep(const tdoa_beam_geometry &g, int Dmax, const tdoa_beam_source &source, int L,
+                    const tdoa_beam_targets &targets, float loading, const float *tab, float *tail,
+                    const tdoa_beam_outputs &out, void *stream)
 {
+    const int64_t rows = source.rows;
+    const int Kt = targets.Kt;
     if (rows <= 0)
         return 0;
-    if (Kt < 1 || Kt > TDOA_SEP_MAX_TARGETS || !tab || (pos && !tail))
+    if (Kt < 1 || Kt > TDOA_SEP_MAX_TARGETS || !tab || (source.pos && !tail))
         return tdoa_set_error(TDOA_ERR_INVALID, "sep: launch arguments");
     const size_t lds = SEP_HEAD_BYTES + tdoa_sep_lds(g.num_mics, L, Kt);
-    sep_kargs a{};
-    a.g = g;
-    a.src = src;
-    a.cl = capture_len;
-    a.pos = pos;
-    a.count = count;
-    a.xy = xy;
-    a.tracks = tracks;
-    a.tab = tab;
-    a.tail = tail;
-    a.audio = out.audio;
-    a.delays = out.delays;
-    a.active = out.active;
-    a.block_start = pos ? out.block_start : nullptr;
-    a.loading = loading;
-    a.Dmax = Dmax;
-    a.L = L;
-    a.min_status = min_status;
+    const sep_kargs a{g, source, targets, tab, tail, out, loading, Dmax, L};
     hipStream_t st = (hipStream_t)stream;
-    if (!pos)
+    if (!source.pos)
         return launch_kt<frame_loader>(a, rows, Kt, lds, st);
-    return pcm16 ? launch_kt<ring_loader<int16_t>>(a, rows, Kt, lds, st)
-                 : launch_kt<ring_loader<uint8_t>>(a, rows, Kt, lds, st);
+    return source.pcm16 ? launch_kt<ring_loader<int16_t>>(a, rows, Kt, lds, st)
+                        : launch_kt<ring_loader<uint8_t>>(a, rows, Kt, lds, st);
 }

@@ -43,10 +43,8 @@ int tdoa_sep_table(int L, float *tab)
 
 int tdoa_sep_check(const char *fn, int Dmax, int L, int32_t Kt, float loading, const void *out, const void *audio)
 {
-    if (!out || !audio)
-        return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument (outputs.audio is required)", fn);
-    if (Kt < 1 || Kt > TDOA_SEP_MAX_TARGETS)
-        return tdoa_fail(TDOA_ERR_INVALID, "%s: Kt %d outside 1..%d", fn, (int)Kt, TDOA_SEP_MAX_TARGETS);
+    if (const int rc = tdoa_beam_check_outputs(fn, Kt, TDOA_SEP_MAX_TARGETS, out, audio))
+        return rc;
     // (the negated comparison is also true for a NaN)
     if (!(loading >= TDOA_SEP_LOADING_MIN && loading <= TDOA_SEP_LOADING_MAX))
         return tdoa_fail(TDOA_ERR_INVALID, "%s: loading %g outside [%g, %g]", fn, (double)loading,

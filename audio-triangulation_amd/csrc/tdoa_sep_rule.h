@@ -24,12 +24,10 @@ inline size_t tdoa_sep_lds(int M, int L, int Kt) { return (size_t)tdoa_sep_bufs(
 int tdoa_sep_check(const char *fn, int Dmax, int L, int32_t Kt, float loading, const void *out, const void *audio);
 
 // the launcher of k_sep (tdoa_sep.hip): one workgroup per row, blocks of L
-// samples.  A ring launch (pos set) reads T [rows][capture_len][M] samples at
-// `src` behind the device clock *pos, overlap-adds into tail [rows][4][L/2] and
-// writes audio [rows][Kt][L/2]; a block launch reads int16 [rows][M][L] and
-// writes audio [rows][Kt][L].  Targets as tdoa_launch_beam takes them.  tab: the
-// device copy of tdoa_sep_table(L).
-int tdoa_launch_sep(const tdoa_beam_geometry &g, int Dmax, const void *src, bool pcm16, int64_t capture_len,
-                    const int64_t *pos, int64_t rows, int L, const int32_t *count, const float *xy,
-                    const tdoa_track *tracks, int32_t min_status, int32_t Kt, float loading, const float *tab,
-                    float *tail, const tdoa_beam_outputs &out, void *stream);
+// samples.  A ring launch overlap-adds into tail [rows][4][L/2] and writes
+// audio [rows][Kt][L/2]; a block launch reads int16 [rows][M][L] and writes
+// audio [rows][Kt][L].  Source and targets as tdoa_launch_beam takes them
+// (tdoa_beam_rule.h).  tab: the device copy of tdoa_sep_table(L).
+int tdoa_launch_sep(const tdoa_beam_geometry &g, int Dmax, const tdoa_beam_source &source, int L,
+                    const tdoa_beam_targets &targets, float loading, const float *tab, float *tail,
+                    const tdoa_beam_outputs &out, void *stream);

@@ -598,22 +598,43 @@ extern "C" int tdoa_stream_tracks_device(tdoa_stream *st, const tdoa_track **tra
     return TDOA_OK;
 }
 
+// What tdoa_stream_beam and tdoa_stream_sep share, before and after their own
+// argument checks: the pipeline's beamformer geometry ...
+static int stream_beam_open(tdoa_stream *st, const char *fn, const tdoa_beam_outputs *out, tdoa_beam_geometry *g,
+                            int *Dmax, const float **fir)
+{
+    if (!st || !out)
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: NULL argument", fn);
+    return tdoa_ctx_beam(st->ctx, fn, g, Dmax, fir);
+}
+
+// ... and its capture rings as a launch's source, the caller's xy -- or, xy
+// null, the track table -- as its targets
+static int stream_beam_io(tdoa_stream *st, const char *fn, const int32_t *count, const float *xy, int32_t Kt,
+                          int32_t min_status, tdoa_beam_source *source, tdoa_beam_targets *targets)
+{
+    if (!xy && !st->track_mem)
+        return tdoa_fail(TDOA_ERR_INVALID, "%s: no xy and no track table yet (tdoa_stream_track makes it)", fn);
+    *source = tdoa_beam_source{st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S};
+    *targets = tdoa_beam_targets{count, xy, xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt};
+    return TDOA_OK;
+}
+
 extern "C" int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt,
                                 int32_t min_status, const tdoa_beam_outputs *out, void *stream)
 {
-    if (!st || !out)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_beam: NULL argument");
     tdoa_beam_geometry g;
     int Dmax = 0;
     const float *fir = nullptr;
-    if (const int rc = tdoa_ctx_beam(st->ctx, "tdoa_stream_beam", &g, &Dmax, &fir))
+    tdoa_beam_source source;
+    tdoa_beam_targets targets;
+    if (const int rc = stream_beam_open(st, "tdoa_stream_beam", out, &g, &Dmax, &fir))
         return rc;
     const int hop = st->sp.H, A = Dmax + TDOA_BEAM_HALF;
     if (const int rc = tdoa_beam_check("tdoa_stream_beam", g, Dmax, hop, Kt, out, out->audio, true))
         return rc;
-    if (!xy && !st->track_mem)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_beam: no xy and no track table yet (tdoa_stream_track "
-                                           "makes it)");
+    if (const int rc = stream_beam_io(st, "tdoa_stream_beam", count, xy, Kt, min_status, &source, &targets))
+        return rc;
     // a block reaches hop + A + 7 samples back from the clock and Dmax + 8 past
     // its last output; one more hop is the producer's margin
     const int64_t need = 2 * (int64_t)hop + A + Dmax + 16;
@@ -623,26 +644,24 @@ extern "C" int tdoa_stream_beam(tdoa_stream *st, const int32_t *count, const flo
     if (st->hop == 0)  // no step since creation or reset: the clock has not moved
         return TDOA_OK;
     HIP_TRY(hipSetDevice(st->device));
-    return tdoa_launch_beam(g, Dmax, st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S, hop, count, xy,
-                            xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt, fir, *out, stream);
+    return tdoa_launch_beam(g, Dmax, source, hop, targets, fir, *out, stream);
 }
 
 extern "C" int tdoa_stream_sep(tdoa_stream *st, const int32_t *count, const float *xy, int32_t Kt, int32_t min_status,
                                float loading, const tdoa_beam_outputs *out, void *stream)
 {
-    if (!st || !out)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: NULL argument");
     tdoa_beam_geometry g;
     int Dmax = 0;
     const float *fir = nullptr;
-    if (const int rc = tdoa_ctx_beam(st->ctx, "tdoa_stream_sep", &g, &Dmax, &fir))
+    tdoa_beam_source source;
+    tdoa_beam_targets targets;
+    if (const int rc = stream_beam_open(st, "tdoa_stream_sep", out, &g, &Dmax, &fir))
         return rc;
     const int hop = st->sp.H, L = 2 * hop;
     if (const int rc = tdoa_sep_check("tdoa_stream_sep", Dmax, L, Kt, loading, out, out->audio))
         return rc;
-    if (!xy && !st->track_mem)
-        return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: no xy and no track table yet (tdoa_stream_track "
-                                           "makes it)");
+    if (const int rc = stream_beam_io(st, "tdoa_stream_sep", count, xy, Kt, min_status, &source, &targets))
+        return rc;
     // a block reaches L = 2 hop samples back from the clock; one more hop is the producer's margin
     if (st->sp.capture_len < 3 * (int64_t)hop)
         return tdoa_fail(TDOA_ERR_INVALID, "tdoa_stream_sep: capture_len %lld < 3 hop = %lld",
@@ -671,9 +690,7 @@ extern "C" int tdoa_stream_sep(tdoa_stream *st, const int32_t *count, const floa
     if (clear && hipMemsetAsync(tail, 0, tail_bytes, (hipStream_t)stream) != hipSuccess)
         return tdoa_fail(TDOA_ERR_HIP, "tdoa_stream_sep: clearing the tails failed");
     st->sep_kt = Kt;
-    return tdoa_launch_sep(g, Dmax, st->sp.capture, st->pcm16, st->sp.capture_len, st->sp.pos, st->S, L, count, xy,
-                           xy ? nullptr : st->track_mem.get<tdoa_track>(), min_status, Kt, loading,
-                           st->sep_mem.get<float>(), tail, *out, stream);
+    return tdoa_launch_sep(g, Dmax, source, L, targets, loading, st->sep_mem.get<float>(), tail, *out, stream);
 }
 
 extern "C" int tdoa_stream_destroy(tdoa_stream *st)

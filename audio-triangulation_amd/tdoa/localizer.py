@@ -409,70 +409,15 @@ class Localizer:
                                       C.c_void_p(st.cuda_stream)), "tdoa_track_batch")
         return outputs
 
-    def beam_batch(self, frames: torch.Tensor, xy: torch.Tensor, count: torch.Tensor | None = None,
-                   outputs=None, stream=None) -> dict:
-        """Beamformed audio of up to 8 targets per frame (tdoa_beam_batch, kernel
-        k_beam; the rule is in include/tdoa.h, "Listening").
-
-        frames: int16 [B][M][N] as localize() takes them; xy: float32
-        [B][Kt][2] plane coordinates (a localize() xy / xy_ls, a peaks() row);
-        count: int32 [B], target k of frame b valid for k < count[b] (None: all
-        Kt) and finite coordinates.  outputs: a dict of tensors to write (audio
-        float32 [B][Kt][N], required; delays int32 [B][Kt][M]; active uint8
-        [B][Kt]) -- fresh ones by default.  Asynchronous on `stream` (default:
-        the current stream)."""
-        dev = self.torch_device
-        M, N = self.dims.M, self.dims.N
-        if frames.dtype != torch.int16 or frames.dim() != 3 or tuple(frames.shape[1:]) != (M, N):
-            raise ValueError(f"frames must be int16 [B][{M}][{N}]")
-        B = frames.shape[0]
-        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != B or xy.shape[2] != 2:
-            raise ValueError("xy must be float32 [B][Kt][2]")
-        Kt = xy.shape[1]
-        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (B,)):
-            raise ValueError("count must be int32 [B]")
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
-        want = {"audio": (torch.float32, (B, Kt, N)), "delays": (torch.int32, (B, Kt, M)),
-                "active": (torch.uint8, (B, Kt))}
-        if outputs is None:
-            with torch.cuda.stream(st):
-                outputs = {k: torch.empty(shp, dtype=dt, device=dev) for k, (dt, shp) in want.items()}
-        if "audio" not in outputs:
-            raise ValueError("outputs[\"audio\"] is required")
-        for name, t in outputs.items():
-            if name not in want or t.dtype != want[name][0] or tuple(t.shape) != want[name][1]:
-                raise ValueError(f"outputs[{name!r}] must be {want.get(name)}")
-        for t in (frames, xy, count, *outputs.values()):
-            if t is not None and (t.device != dev or not t.is_contiguous()):
-                raise ValueError(f"every tensor must be contiguous on {dev}")
-        if B == 0:  # nothing to launch (and empty tensors have no address to pass)
-            return outputs
-        o = BeamOutputs(*[None if outputs.get(n) is None else outputs[n].data_ptr() for n, _ in BeamOutputs._fields_])
-        check(load().tdoa_beam_batch(self._ctx, _ptr(frames), B, _ptr(count), _ptr(xy) if xy.numel() else None, Kt,
-                                     C.byref(o), C.c_void_p(st.cuda_stream)), "tdoa_beam_batch")
-        return outputs
-
-    def sep_batch(self, frames: torch.Tensor, xy: torch.Tensor, count: torch.Tensor | None = None,
-                  loading: float = _lib.SEP_LOADING, outputs=None, stream=None) -> dict:
-        """One null-steered STFT block per frame and target (tdoa_sep_batch,
-        kernel k_sep; the rule is in include/tdoa.h, "Separating"): channel k
-        has unit gain on target k and nulls on the frame's other valid targets.
-
-        frames: int16 [B][M][L], L a power of two in 128..2048 with L >= 8 Dmax
-        -- frame_len or any other block length: a call whose L differs from the
-        context's (sep_block()) sets it first (tdoa_sep_set_block: an upload and
-        a device synchronisation, once per change); xy: float32 [B][Kt][2]
-        plane coordinates, Kt <= 4; count:
-        int32 [B] (None: all Kt); loading: the diagonal loading delta in
-        [1e-4, 1e4].  outputs: a dict of tensors to write (audio float32
-        [B][Kt][L], required -- the synthesis-windowed block, to be
-        overlap-added with its half-overlapped neighbours; delays int32
-        [B][Kt][M]; active uint8 [B][Kt]) -- fresh ones by default.
-        Asynchronous on `stream` (default: the current stream)."""
+    def _steered_batch(self, frames, N, xy, count, outputs, stream, name: str, call) -> dict:
+        """What beam_batch() and sep_batch() share: frames int16 [B][M][N] (N an
+        int, or None: any length), xy, count and the outputs validated, the
+        outputs made where none were given, then -- B > 0 -- call(Kt,
+        BeamOutputs pointer, stream pointer) -> the library's return code."""
         dev = self.torch_device
         M = self.dims.M
-        if frames.dtype != torch.int16 or frames.dim() != 3 or frames.shape[1] != M:
-            raise ValueError(f"frames must be int16 [B][{M}][L]")
+        if frames.dtype != torch.int16 or frames.dim() != 3 or tuple(frames.shape[1:]) != (M, N or frames.shape[2]):
+            raise ValueError(f"frames must be int16 [B][{M}][{N or 'L'}]")
         B, N = frames.shape[0], frames.shape[2]
         if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != B or xy.shape[2] != 2:
             raise ValueError("xy must be float32 [B][Kt][2]")
@@ -495,12 +440,50 @@ class Localizer:
                 raise ValueError(f"every tensor must be contiguous on {dev}")
         if B == 0:  # nothing to launch (and empty tensors have no address to pass)
             return outputs
-        if N != self.sep_block():
-            check(load().tdoa_sep_set_block(self._ctx, N), "tdoa_sep_set_block")
         o = BeamOutputs(*[None if outputs.get(n) is None else outputs[n].data_ptr() for n, _ in BeamOutputs._fields_])
-        check(load().tdoa_sep_batch(self._ctx, _ptr(frames), B, _ptr(count), _ptr(xy) if xy.numel() else None, Kt,
-                                    float(loading), C.byref(o), C.c_void_p(st.cuda_stream)), "tdoa_sep_batch")
+        check(call(Kt, C.byref(o), C.c_void_p(st.cuda_stream)), name)
         return outputs
+
+    def beam_batch(self, frames: torch.Tensor, xy: torch.Tensor, count: torch.Tensor | None = None,
+                   outputs=None, stream=None) -> dict:
+        """Beamformed audio of up to 8 targets per frame (tdoa_beam_batch, kernel
+        k_beam; the rule is in include/tdoa.h, "Listening").
+
+        frames: int16 [B][M][N] as localize() takes them; xy: float32
+        [B][Kt][2] plane coordinates (a localize() xy / xy_ls, a peaks() row);
+        count: int32 [B], target k of frame b valid for k < count[b] (None: all
+        Kt) and finite coordinates.  outputs: a dict of tensors to write (audio
+        float32 [B][Kt][N], required; delays int32 [B][Kt][M]; active uint8
+        [B][Kt]) -- fresh ones by default.  Asynchronous on `stream` (default:
+        the current stream)."""
+        return self._steered_batch(frames, self.dims.N, xy, count, outputs, stream, "tdoa_beam_batch",
+                                   lambda Kt, out, st: load().tdoa_beam_batch(
+                                       self._ctx, _ptr(frames), frames.shape[0], _ptr(count),
+                                       _ptr(xy) if xy.numel() else None, Kt, out, st))
+
+    def sep_batch(self, frames: torch.Tensor, xy: torch.Tensor, count: torch.Tensor | None = None,
+                  loading: float = _lib.SEP_LOADING, outputs=None, stream=None) -> dict:
+        """One null-steered STFT block per frame and target (tdoa_sep_batch,
+        kernel k_sep; the rule is in include/tdoa.h, "Separating"): channel k
+        has unit gain on target k and nulls on the frame's other valid targets.
+
+        frames: int16 [B][M][L], L a power of two in 128..2048 with L >= 8 Dmax
+        -- frame_len or any other block length: a call whose L differs from the
+        context's (sep_block()) sets it first (tdoa_sep_set_block: an upload and
+        a device synchronisation, once per change); xy: float32 [B][Kt][2]
+        plane coordinates, Kt <= 4; count:
+        int32 [B] (None: all Kt); loading: the diagonal loading delta in
+        [1e-4, 1e4].  outputs: a dict of tensors to write (audio float32
+        [B][Kt][L], required -- the synthesis-windowed block, to be
+        overlap-added with its half-overlapped neighbours; delays int32
+        [B][Kt][M]; active uint8 [B][Kt]) -- fresh ones by default.
+        Asynchronous on `stream` (default: the current stream)."""
+        def call(Kt, out, st):
+            if frames.shape[2] != self.sep_block():
+                check(load().tdoa_sep_set_block(self._ctx, frames.shape[2]), "tdoa_sep_set_block")
+            return load().tdoa_sep_batch(self._ctx, _ptr(frames), frames.shape[0], _ptr(count),
+                                         _ptr(xy) if xy.numel() else None, Kt, float(loading), out, st)
+        return self._steered_batch(frames, None, xy, count, outputs, stream, "tdoa_sep_batch", call)
 
     def sep_block(self) -> int:
         """The block length sep_batch() runs at (tdoa_sep_get_block; 0: none yet)."""

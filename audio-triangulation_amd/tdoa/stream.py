@@ -104,7 +104,7 @@ import torch
 
 from ._lib import (BEAM_MAX_TARGETS, MAX_TRACKS, SEP_LOADING, SEP_MAX_TARGETS, STREAM_TRIGGER_VAR_PCM16, TRACK_FIELDS,
                    BeamOutputs, PeaksOutputs, PeaksParams, StreamOutputs, StreamOutputsF, TrackOutputs, check, load, track_params)
-from .localizer import Localizer
+from .localizer import Localizer, _ptr
 
 
 class StreamPipeline:
@@ -342,6 +342,41 @@ class StreamPipeline:
         shapes (8 mics x 2048, 4 x 4096), k_direct_mfma / k_direct."""
         return (load().tdoa_stream_kernel(self._h) or b"").decode()
 
+    def _target_count(self, xy, count, num_targets, default: int) -> int:
+        """Kt of a beam() / sep() call, its xy / count / num_targets validated."""
+        if xy is None:
+            if count is not None:
+                raise ValueError("count goes with xy; the track table's targets are chosen by min_status")
+            return default if num_targets is None else int(num_targets)
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
+            raise ValueError("xy must be float32 [S][Kt][2]")
+        if num_targets is not None and int(num_targets) != xy.shape[1]:
+            raise ValueError("num_targets differs from xy's Kt")
+        if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.S,)):
+            raise ValueError("count must be int32 [S]")
+        for t in (xy, count):
+            if t is not None and (t.device != self.loc.torch_device or not t.is_contiguous()):
+                raise ValueError("xy and count must be contiguous on the localizer's device")
+        return xy.shape[1]
+
+    def _steered(self, cache: dict, Kt: int, name: str, call) -> dict:
+        """The output tensors of `cache` for Kt (made at first use), filled by
+        call(BeamOutputs pointer, stream pointer) -> the library's return code."""
+        dev = self.loc.torch_device
+        o = cache.get(Kt)
+        if o is None:
+            S, n, M = self.S, max(Kt, 0), self.loc.dims.M
+            o = {"audio": torch.zeros((S, n, self.hop), dtype=torch.float32, device=dev),
+                 "delays": torch.zeros((S, n, M), dtype=torch.int32, device=dev),
+                 "active": torch.zeros((S, n), dtype=torch.uint8, device=dev),
+                 "block_start": torch.zeros(1, dtype=torch.int64, device=dev)}
+            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
+            self.stream.wait_stream(torch.cuda.current_stream(dev))
+        s = BeamOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in BeamOutputs._fields_])
+        check(call(C.byref(s), C.c_void_p(self.stream.cuda_stream)), name)
+        cache[Kt] = o  # kept only once the library accepted the arguments
+        return o
+
     def beam(self, xy: torch.Tensor | None = None, count: torch.Tensor | None = None,
              num_targets: int | None = None, min_status: int = 2) -> dict:
         """One block of beamformed audio per stream and target
@@ -361,37 +396,9 @@ class StreamPipeline:
         (the codes, -1 invalid), active uint8 [S][Kt] and block_start int64 [1],
         the absolute sample of audio[..., 0] = clock - hop - A; consecutive
         hops' blocks abut.  Every stream is written, listed by the step or not."""
-        dev = self.loc.torch_device
-        if xy is not None:
-            if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
-                raise ValueError("xy must be float32 [S][Kt][2]")
-            if num_targets is not None and int(num_targets) != xy.shape[1]:
-                raise ValueError("num_targets differs from xy's Kt")
-            Kt = xy.shape[1]
-            if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.S,)):
-                raise ValueError("count must be int32 [S]")
-            for t in (xy, count):
-                if t is not None and (t.device != dev or not t.is_contiguous()):
-                    raise ValueError("xy and count must be contiguous on the localizer's device")
-        else:
-            if count is not None:
-                raise ValueError("count goes with xy; the track table's targets are chosen by min_status")
-            Kt = BEAM_MAX_TARGETS if num_targets is None else int(num_targets)
-        o = self._beams.get(Kt)
-        if o is None:
-            S, n, M = self.S, max(Kt, 0), self.loc.dims.M
-            o = {"audio": torch.zeros((S, n, self.hop), dtype=torch.float32, device=dev),
-                 "delays": torch.zeros((S, n, M), dtype=torch.int32, device=dev),
-                 "active": torch.zeros((S, n), dtype=torch.uint8, device=dev),
-                 "block_start": torch.zeros(1, dtype=torch.int64, device=dev)}
-            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-        s = BeamOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in BeamOutputs._fields_])
-        check(load().tdoa_stream_beam(self._h, None if count is None else C.c_void_p(count.data_ptr()),
-                                      None if xy is None else C.c_void_p(xy.data_ptr()), Kt, int(min_status),
-                                      C.byref(s), C.c_void_p(self.stream.cuda_stream)), "tdoa_stream_beam")
-        self._beams[Kt] = o  # kept only once the library accepted the arguments
-        return o
+        Kt = self._target_count(xy, count, num_targets, BEAM_MAX_TARGETS)
+        return self._steered(self._beams, Kt, "tdoa_stream_beam", lambda out, st: load().tdoa_stream_beam(
+            self._h, _ptr(count), _ptr(xy), Kt, int(min_status), out, st))
 
     def sep(self, xy: torch.Tensor | None = None, count: torch.Tensor | None = None,
             num_targets: int | None = None, min_status: int = 2, loading: float = SEP_LOADING) -> dict:
@@ -412,38 +419,9 @@ class StreamPipeline:
         clock - 2 hop; delays int32 [S][Kt][M]; active uint8 [S][Kt].
         Consecutive hops' blocks abut; a call with another Kt starts the
         overlap-add afresh, and so does reset()."""
-        dev = self.loc.torch_device
-        if xy is not None:
-            if xy.dtype != torch.float32 or xy.dim() != 3 or xy.shape[0] != self.S or xy.shape[2] != 2:
-                raise ValueError("xy must be float32 [S][Kt][2]")
-            if num_targets is not None and int(num_targets) != xy.shape[1]:
-                raise ValueError("num_targets differs from xy's Kt")
-            Kt = xy.shape[1]
-            if count is not None and (count.dtype != torch.int32 or tuple(count.shape) != (self.S,)):
-                raise ValueError("count must be int32 [S]")
-            for t in (xy, count):
-                if t is not None and (t.device != dev or not t.is_contiguous()):
-                    raise ValueError("xy and count must be contiguous on the localizer's device")
-        else:
-            if count is not None:
-                raise ValueError("count goes with xy; the track table's targets are chosen by min_status")
-            Kt = SEP_MAX_TARGETS if num_targets is None else int(num_targets)
-        o = self._seps.get(Kt)
-        if o is None:
-            S, n, M = self.S, max(Kt, 0), self.loc.dims.M
-            o = {"audio": torch.zeros((S, n, self.hop), dtype=torch.float32, device=dev),
-                 "delays": torch.zeros((S, n, M), dtype=torch.int32, device=dev),
-                 "active": torch.zeros((S, n), dtype=torch.uint8, device=dev),
-                 "block_start": torch.zeros(1, dtype=torch.int64, device=dev)}
-            # the allocator's fills ran on the current stream: they precede the kernel on self.stream
-            self.stream.wait_stream(torch.cuda.current_stream(dev))
-        s = BeamOutputs(*[o[n].data_ptr() if o[n].numel() else None for n, _ in BeamOutputs._fields_])
-        check(load().tdoa_stream_sep(self._h, None if count is None else C.c_void_p(count.data_ptr()),
-                                     None if xy is None else C.c_void_p(xy.data_ptr()), Kt, int(min_status),
-                                     float(loading), C.byref(s), C.c_void_p(self.stream.cuda_stream)),
-              "tdoa_stream_sep")
-        self._seps[Kt] = o  # kept only once the library accepted the arguments
-        return o
+        Kt = self._target_count(xy, count, num_targets, SEP_MAX_TARGETS)
+        return self._steered(self._seps, Kt, "tdoa_stream_sep", lambda out, st: load().tdoa_stream_sep(
+            self._h, _ptr(count), _ptr(xy), Kt, int(min_status), float(loading), out, st))
 
     def est_ptr(self):
         """(device address, is_float) of the EMA state: int64 [S][P][K] (DIRECT)

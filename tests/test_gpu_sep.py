@@ -141,8 +141,16 @@ def test_block_form_non_finite_and_coincident_targets(locs):
 
 # ---------------------------------------------------------------- the streaming form
 NS, HOP, HOPS, KT = 5, 64, 10, 3
-CAP_LEN = 385  # >= frame_len + 2 hop = 384; 385 * 3 elements per stream: no multiple of 16 bytes in either type
-STREAM_CASES = [("direct", "triggered", np.uint8), ("gcc_phat", "continuous", np.int16)]
+# (engine, mode, dtype, M, capture_len), capture_len >= frame_len + 2 hop = 384 and shorter than the 10 hops.
+# 385 * 3 elements per stream are no multiple of 16 bytes in either type: most streams' rows take element loads
+# alone.  392 * 4 elements are 1568 and 3136 bytes: every stream's ring starts 16-byte aligned and the 16-byte
+# vectors carry the block, up to the seam at the ring's end.
+CAP_LEN = 385
+MICS4 = SC.circle(4, 0.1)  # Dmax = 11 at 16 kHz: L = 128 >= 8 Dmax
+STREAM_CASES = [pytest.param("direct", "triggered", np.uint8, 3, CAP_LEN, id="direct-triggered-uint8"),
+                pytest.param("gcc_phat", "continuous", np.int16, 3, CAP_LEN, id="gcc_phat-continuous-int16"),
+                pytest.param("direct", "triggered", np.uint8, 4, 392, id="direct-triggered-uint8-392x4"),
+                pytest.param("gcc_phat", "continuous", np.int16, 4, 392, id="gcc_phat-continuous-int16-392x4")]
 
 
 def _history(T, M, dtype, seed):
@@ -156,11 +164,11 @@ def _history(T, M, dtype, seed):
     return np.clip(np.rint(8000 * x), -32767, 32767).astype(np.int16)
 
 
-def _pipe(lc, dtype, mode, use_graph=True):
+def _pipe(lc, dtype, mode, use_graph=True, cap_len=CAP_LEN):
     M = lc.dims.M
     dt = torch.uint8 if dtype == np.uint8 else torch.int16
-    flat = torch.zeros(NS * CAP_LEN * M + (4 if dt == torch.uint8 else 0), dtype=dt, device="cuda")
-    ring = flat[:NS * CAP_LEN * M].view(NS, CAP_LEN, M)
+    flat = torch.zeros(NS * cap_len * M + (4 if dt == torch.uint8 else 0), dtype=dt, device="cuda")
+    ring = flat[:NS * cap_len * M].view(NS, cap_len, M)
     kw = dict(mode="continuous", activity_var=0) if mode == "continuous" else {}
     return StreamPipeline(lc, ring, hop=HOP, use_graph=use_graph, **kw)
 
@@ -195,12 +203,13 @@ def _check_hop(g, want, restated, label):
     return tol
 
 
-@pytest.mark.parametrize("engine,mode,dtype", STREAM_CASES)
-def test_stream_sep_with_explicit_targets(engine, mode, dtype):
-    M = 3
-    lc = _loc(M, 256, engine, "pcm16" if dtype == np.int16 else "adc8")
+@pytest.mark.parametrize("engine,mode,dtype,M,cap_len", STREAM_CASES)
+def test_stream_sep_with_explicit_targets(engine, mode, dtype, M, cap_len):
+    lc = _loc(M, 256, engine, "pcm16" if dtype == np.int16 else "adc8", mics=MICS4 if M == 4 else None)
     mics, fs, c = _geom(lc)
-    assert (CAP_LEN * M * np.dtype(dtype).itemsize) % 16 != 0 and CAP_LEN < HOPS * HOP and CAP_LEN >= 3 * HOP
+    assert S.block_ok(2 * HOP, R.dmax(mics, fs, c))
+    assert ((cap_len * M * np.dtype(dtype).itemsize) % 16 == 0) == (M == 4)
+    assert cap_len < HOPS * HOP and cap_len >= 3 * HOP
     hist = _history(HOPS * HOP, M, dtype, 5 + np.dtype(dtype).itemsize)
     src = torch.from_numpy(hist).cuda()
     rng = np.random.default_rng(17)
@@ -209,7 +218,8 @@ def test_stream_sep_with_explicit_targets(engine, mode, dtype):
     count = np.array([KT, KT, KT - 1, 0, KT], np.int32)
     d_xy, d_cnt = torch.from_numpy(xy).cuda(), torch.from_numpy(count).cuda()
     ref, c64 = _refs(mics, fs, c, hist, KT)
-    pipe = _pipe(lc, dtype, mode)
+    pipe = _pipe(lc, dtype, mode, cap_len=cap_len)
+    assert pipe.capture.data_ptr() % 16 == 0  # (with the stride, what lets the 392 x 4 rings take vectors)
     # before any step: TDOA_OK, nothing is launched
     o = pipe.sep(d_xy, d_cnt)
     assert o["audio"].shape == (NS, KT, HOP) and o["delays"].shape == (NS, KT, M) and o["active"].shape == (NS, KT)
@@ -235,8 +245,8 @@ def test_stream_sep_with_explicit_targets(engine, mode, dtype):
         if h >= 7:
             assert (g["audio"][0, 1:] == 0).all()  # invalid for two blocks: block and tail are zeros
         blocks.append(g["audio"])
-        lo = (h * HOP - 2 * HOP) % CAP_LEN
-        wrapped += h >= 2 and lo + 2 * HOP > CAP_LEN
+        lo = (h * HOP - 2 * HOP) % cap_len
+        wrapped += h >= 2 and lo + 2 * HOP > cap_len
     assert wrapped >= 1  # a staged block crossed the ring's end
     # the blocks abut: their concatenation is the overlap-add of the block form over the history.  Where
     # every block has both its neighbours, [hop, T - 2 hop), its relative error is at most the largest of
@@ -263,16 +273,15 @@ def test_stream_sep_with_explicit_targets(engine, mode, dtype):
     lc.close()
 
 
-@pytest.mark.parametrize("engine,mode,dtype", STREAM_CASES)
-def test_reset_zeroes_the_tails(engine, mode, dtype):
-    M = 3
-    lc = _loc(M, 256, engine, "pcm16" if dtype == np.int16 else "adc8")
+@pytest.mark.parametrize("engine,mode,dtype,M,cap_len", STREAM_CASES)
+def test_reset_zeroes_the_tails(engine, mode, dtype, M, cap_len):
+    lc = _loc(M, 256, engine, "pcm16" if dtype == np.int16 else "adc8", mics=MICS4 if M == 4 else None)
     hist = _history(4 * HOP, M, dtype, 31)
     src = torch.from_numpy(hist).cuda()
     xy = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, (NS, 2, 2)).astype(np.float32)).cuda()
     first = {}
     for warm in (0, 3):
-        pipe = _pipe(lc, dtype, mode)
+        pipe = _pipe(lc, dtype, mode, cap_len=cap_len)
         for h in range(warm):
             _produce(pipe, src, h + 1)
             pipe.step()

@@ -39,9 +39,14 @@ __device__ __forceinline__ f2 mul_i(f2 a) { return f2{-a.y, a.x}; }
 __device__ __forceinline__ f2 mul_mi(f2 a) { return f2{a.y, -a.x}; }
 __device__ __forceinline__ f2 ldtw(const float *tw, int k) { return f2{tw[2 * k], tw[2 * k + 1]}; }
 
-// In-place complex FFT of length n (256 <= n <= 4096, power of two) held in
-// LDS: Stockham radix-4 passes (one radix-2 pass last when log2 n is odd),
-// each pass staged through registers so one buffer suffices.  tw = W_n^k.
+// In-place complex FFT of length n (128 <= n <= 4096, power of two; the
+// separator, tdoa_sep.hip, is the caller below 256) held in LDS: Stockham
+// radix-4 passes (one radix-2 pass last when log2 n is odd), each pass staged
+// through registers so one buffer suffices.  tw = W_n^k, n entries.  Nothing in
+// it depends on n >= 256: a thread takes the butterflies j = tid + 256 b < n / 4
+// (n / 2 in the radix-2 pass), none at all where tid is past them, and still
+// reaches every barrier; the twiddle indices stay below 3 n / 4.  The caller's
+// data must be published (a barrier) before the call; it ends with one.
 template <bool INV>
 __device__ void fft_inplace(f2 *buf, int n, const float *__restrict__ tw)
 {

@@ -33,13 +33,22 @@ def circle(M, r):
 
 # M -> mics (None: the reference triangle).  At 16 kHz the widest, the 8-mic
 # circle of radius 0.15 m, has Dmax = 15: 8 Dmax <= 128.
-MICS = {2: np.array([[-0.1, 0.0], [0.1, 0.0]], np.float32), 3: None, 5: circle(5, 0.12), 8: circle(8, 0.15)}
+MICS = {2: np.array([[-0.1, 0.0], [0.1, 0.0]], np.float32), 3: None, 5: circle(5, 0.12), 6: circle(6, 0.13),
+        7: circle(7, 0.14), 8: circle(8, 0.15)}
 
 # (M, L, Kt): the smallest shapes that reach each path -- one mic pair / an odd
 # mic / more target pairs than mic pairs (2, 128, 2 has one of each; 3, 256, 4
 # has two target pairs over two mic pairs, the second with an odd mic), an odd
-# Kt, four full pairs, a radix-2 tail (128) and none (256), and the LDS maximum
-BLOCK_SHAPES = [(2, 128, 2), (3, 128, 2), (3, 256, 4), (5, 256, 3), (8, 256, 4)]
+# Kt, four full pairs, a radix-2 tail (128) and none (256), and the LDS maximum.
+# From L = 512 on a thread owns several bins (k, k + 256, ..) and the FFT's
+# butterflies fill (1024: n / 4 = 256 threads exactly) or exceed (2048) one pass
+# of the workgroup; log2 L is odd at 512 and 2048 (radix-2 tail), even at 1024.
+# Each of those lengths with an invalid target (the counts of block_case), an
+# odd mic, an odd Kt, one target, more target pairs than mic pairs, and above
+# 64 KiB of LDS with an odd mic (7, 2048, 4).
+BLOCK_SHAPES = [(2, 128, 2), (3, 128, 2), (3, 256, 4), (5, 256, 3), (8, 256, 4),
+                (2, 512, 4), (5, 512, 3), (7, 512, 4), (6, 1024, 3), (8, 1024, 4), (2, 1024, 1), (7, 2048, 4),
+                (5, 2048, 3)]
 LDS_MAX_SHAPE = (8, 2048, 4)
 
 

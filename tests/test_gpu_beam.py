@@ -27,7 +27,8 @@ from tdoa.stream import StreamPipeline  # noqa: E402
 
 FS = 48000
 SENT = 0x5A
-MICS = {3: None, 4: synth.square_mics(0.15), 8: synth.circle_mics(8, 0.15)}
+MICS = {2: np.array([[-0.066, 0], [0.066, 0]], np.float32), 3: None, 4: synth.square_mics(0.15),
+        **{M: synth.circle_mics(M, 0.15) for M in (5, 6, 7, 8)}}
 
 
 def _loc(M, N, engine="gcc_phat", fmt="adc8", mics=None):
@@ -132,12 +133,13 @@ def test_batch_errors_leave_outputs_untouched(locs):
 # ---------------------------------------------------------------- the streaming form
 S, HOPS, KT = 5, 8, 3
 
-# (engine, mode, ring type, M, N, hop, capture_len).  capture_len * M is odd in
-# some cases (a stream's ring is then 1- or 2-byte aligned only: element loads)
-# and a multiple of 8 in others (16-byte vectors), and every ring is shorter
-# than the 8 hops: the staged runs wrap it -- from hop 4 at the latest where
-# hop >= 200, at hops 7 and 8 where hop = 64 (capture_len >= N + 2 hop = 384
-# samples there, and six hops are 384).
+# (engine, mode, ring type, M, N, hop, capture_len).  Of the first six,
+# capture_len * M is odd in some cases (a stream's ring is then 1- or 2-byte
+# aligned only: element loads) and a multiple of 8 in others (16-byte vectors
+# in every stream or every other one; RING_16 below says which), and every ring
+# is shorter than the 8 hops: the staged runs wrap it -- from hop 4 at the
+# latest where hop >= 200, at hops 7 and 8 where hop = 64 (capture_len >= N +
+# 2 hop = 384 samples there, and six hops are 384).
 STREAM_CASES = [
     ("direct", "triggered", np.uint8, 3, 256, 64, 385),
     ("direct", "triggered", np.uint8, 3, 1024, 512, 2051),
@@ -145,7 +147,36 @@ STREAM_CASES = [
     ("gcc_phat", "triggered", np.int16, 3, 256, 200, 657),
     ("gcc_phat", "continuous", np.int16, 4, 1024, 512, 2048),
     ("gcc_phat", "continuous", np.uint8, 3, 256, 200, 664),
+    # Every other mic count, on pipelines the streaming tests of those counts create (tests/test_gpu_stream.py,
+    # tests/mic_count_cases.py, tests/stream16_cases.py, tests/stream_long_cases.py).  ring_stage walks a 16-byte
+    # vector's elements over (sample row, mic): 2 mics put eight rows into a uint8 vector; 5, 6 and 7 turn the
+    # row inside a vector at a different place in each; 8 mics are two rows per uint8 vector and one per int16
+    # vector, on the 8 x 2048 pipeline at its hop of 1024 and on 8 x 1024.  The last is the 4 x 4096 pipeline.
+    ("direct", "triggered", np.uint8, 2, 1024, 512, 2049),
+    ("gcc_phat", "continuous", np.int16, 5, 1024, 512, 2056),
+    ("gcc_phat", "continuous", np.int16, 6, 1024, 512, 2049),
+    ("gcc_phat", "continuous", np.uint8, 7, 512, 256, 1040),
+    ("gcc_phat", "triggered", np.uint8, 8, 2048, 1024, 4098),
+    ("gcc_phat", "triggered", np.int16, 8, 1024, 512, 2049),
+    ("gcc_phat", "continuous", np.int16, 4, 4096, 2048, 8195),
 ]
+# (ring type, M, capture_len) of the cases whose rings are multiples of 16 bytes each: every stream's ring then
+# starts as the first does, 16-byte aligned, and the vectors carry its runs up to the seam at the ring's end.
+# In every other case the streams' alignments differ, down to element loads alone.  Both classes in both types.
+RING_16 = {(np.int16, 4, 2048), (np.int16, 5, 2056), (np.uint8, 7, 1040), (np.uint8, 8, 4098), (np.int16, 8, 2049)}
+LONG_FRAME = {(8, 2048): 1024, (4, 4096): 2048}  # the k_f16_ring pipelines and the hop each is run at here
+
+
+def test_stream_cases_reach_every_ring_walk():
+    """What the streaming cases cover together, on their parameters alone."""
+    assert {c[3] for c in STREAM_CASES} == {2, 3, 4, 5, 6, 7, 8}
+    for dtype in (np.uint8, np.int16):
+        mine = [c for c in STREAM_CASES if c[2] == dtype]
+        assert {(c[2], c[3], c[6]) in RING_16 for c in mine} == {False, True}
+        assert any(c[3] == 8 for c in mine)
+        assert any(c[3] in (2, 8) for c in mine) and any(c[3] in (5, 6, 7) for c in mine)
+    for (M, N), hop in LONG_FRAME.items():
+        assert any(c[0] == "gcc_phat" and c[3:6] == (M, N, hop) for c in STREAM_CASES)
 
 
 def _pipe(lc, cap_len, dtype, hop, mode, use_graph):
@@ -187,7 +218,8 @@ def test_stream_beam_equals_reference(engine, mode, dtype, M, N, hop, cap_len):
     bg, mics, fs, c = _geom(lc)
     A, D = R.latency(mics, fs, c)
     assert cap_len >= 2 * hop + A + D + 16 and cap_len < HOPS * hop
-    assert (cap_len * M) % 2 == 1 or (cap_len * M) % 8 == 0
+    # the alignment class the case claims: a stream's ring is a multiple of 16 bytes, or it is not
+    assert ((cap_len * M * np.dtype(dtype).itemsize) % 16 == 0) == ((dtype, M, cap_len) in RING_16)
     hist = BC.history(S, HOPS * hop, M, dtype, 7 * M + hop)
     src = torch.from_numpy(hist).cuda()
     xy, count = _targets(mics, hop)
@@ -199,6 +231,8 @@ def test_stream_beam_equals_reference(engine, mode, dtype, M, N, hop, cap_len):
     runs = {}
     for use_graph in (False, True):
         pipe = _pipe(lc, cap_len, dtype, hop, mode, use_graph)
+        if (M, N) in LONG_FRAME:
+            assert hop == LONG_FRAME[(M, N)] and pipe.kernel == "k_f16_ring"
         # before any step: TDOA_OK, nothing is launched
         o = pipe.beam(d_xy, d_cnt)
         assert o["audio"].shape == (S, KT, hop) and o["delays"].shape == (S, KT, M) and o["active"].shape == (S, KT)

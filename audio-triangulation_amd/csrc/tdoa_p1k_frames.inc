@@ -11,6 +11,12 @@
     constexpr int N = 1024, P = 3, NF = 2 * NW, NT = NW * 64;
     constexpr bool WG4 = NW == 4;
     constexpr bool PRUNE = WG4 && P1K_GRID_PRUNE;
+    // the LDS read depths per call site (tdoa_phat1024.hip, P1K_TWM_* ...):
+    // R in the four roomy transforms, T in the two at the register peak
+    constexpr int TWM_R = PCM16 ? P1K_TWM_ROOMY_PCM16 : P1K_TWM_ROOMY, TWM_T = PCM16 ? P1K_TWM_TIGHT_PCM16 : P1K_TWM_TIGHT;
+    constexpr int TW2_R = PCM16 ? P1K_TW2_ROOMY_PCM16 : P1K_TW2_ROOMY, TW2_T = PCM16 ? P1K_TW2_TIGHT_PCM16 : P1K_TW2_TIGHT;
+    constexpr int ROW_R = PCM16 ? P1K_ROW_ROOMY_PCM16 : P1K_ROW_ROOMY;
+    static_assert(TW2_T == 1 || TW2_T == 2, "the transforms at the register peak keep their twiddles one pair ahead");
     static_assert(!WG4 || NW * P1K_WAVE_LDS + P1K_IMG_LDS4 <= 80 * 1024, "two workgroups must fit a CU's 160 KiB of LDS");
     static_assert(!WG4 || !P1K_GROUPS, "the grouped scan reads its words from LDS");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -204,11 +210,26 @@
             bk = bk < 0 ? 0 : (bk >= K ? K - 1 : bk);
             best[p] = bk - S;
             const int64_t ff = base + 2 * ((ft >> 6) & (NW - 1)) + fhw;
+#if P1K_PRIOR_AHEAD
+            // the four prior values in one LDS round trip: volatile reads at a
+            // clamped index (d <= 127 for a candidate in range), so none sits
+            // in an exec-masked branch with a wait of its own
+            float pr[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const int d = ck[c] > bk ? ck[c] - bk : bk - ck[c];
+                pr[c] = __builtin_bit_cast(float, lds_rd_u32(reinterpret_cast<const uint32_t *>(prior) + (ok[c] ? d : 0)));
+            }
+#pragma unroll
+            for (int c = 0; c < 4; c++)
+                wv[p][c] = ok[c] ? cv[c] * pr[c] : 0.0f;
+#else
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 const int d = ck[c] > bk ? ck[c] - bk : bk - ck[c];
                 wv[p][c] = ok[c] ? cv[c] * prior[ok[c] ? d : 0] : 0.0f;
             }
+#endif
             if (out.scores_f || out.weighted_f) {  // debug / parity outputs (uniform branch)
                 float *sr = out.scores_f ? out.scores_f + (size_t)(ff * P + p) * K : nullptr;
                 float *wr = out.weighted_f ? out.weighted_f + (size_t)(ff * P + p) * K : nullptr;
@@ -231,32 +252,32 @@
         // the mics' rows are requested one at a time, each after the previous
         // one's front end: at the kernel's start the memory system serves every
         // wave's first row (8 MB) instead of all rows at once
-        lean_forward<PCM16>(L, w0, q0, U0, e2, [&] {
+        lean_forward<PCM16, TWM_R, TW2_R>(L, w0, q0, U0, e2, [&] {
             fetch(w1, q1, f, 1);
             balance();
         });
         LEAN_MARK();
         balance();
 #if P1K_W2_EARLY
-        lean_forward<PCM16>(L, w1, q1, U1, e2, [&] {
+        lean_forward<PCM16, TWM_R, TW2_R>(L, w1, q1, U1, e2, [&] {
             fetch(w2, q2, f, 2);
             balance();
         });
 #else
-        lean_forward<PCM16>(L, w1, q1, U1, e2, [&] { balance(); });
+        lean_forward<PCM16, TWM_R, TW2_R>(L, w1, q1, U1, e2, [&] { balance(); });
 #endif
         LEAN_MARK();
         balance();
         {
             f2 v[32];
-            lean_pretwiddle<true>(L, U0, U1, v);  // pair 0: (0, 1)
-            fft_col_lds<true, false>(L, v, L.tileA);
+            lean_pretwiddle<true, TW2_T>(L, U0, U1, v);  // pair 0: (0, 1)
+            fft_col_lds<true, false, TWM_T>(L, v, L.tileA);
 #if !P1K_W2_EARLY
             // mic 2's words: fetched after the pair's column pass, the kernel's
             // register peak (two unit spectra + a working column)
             fetch(w2, q2, f, 2, !P1K_WG4_WQ_LATE);
 #endif
-            lean_row_inv(L, L.tileA, y0, y31);
+            lean_row_inv<16>(L, L.tileA, y0, y31);
         }
         finish_pair(0, y0, y31);
 #if P1K_WG4_WQ_LATE
@@ -264,23 +285,23 @@
 #endif
         LEAN_MARK();
         balance();
-        lean_forward_cross<PCM16>(L, w2, q2, U0, U1, e2);  // pairs 1: (0, 2), 2: (1, 2)
+        lean_forward_cross<PCM16, TWM_T, TW2_T>(L, w2, q2, U0, U1, e2);  // pairs 1: (0, 2), 2: (1, 2)
         LEAN_MARK();
         balance();
         {
             f2 v[32];
-            lean_pretwiddle<false>(L, U0, U0, v);
-            fft_col_lds<true, false>(L, v, L.tileA);
-            lean_row_inv(L, L.tileA, y0, y31);
+            lean_pretwiddle<false, TW2_R>(L, U0, U0, v);
+            fft_col_lds<true, false, TWM_R>(L, v, L.tileA);
+            lean_row_inv<ROW_R>(L, L.tileA, y0, y31);
         }
         finish_pair(1, y0, y31);
         LEAN_MARK();
         balance();
         {
             f2 v[32];
-            lean_pretwiddle<false>(L, U1, U1, v);
-            fft_col_lds<true, false>(L, v, L.tileA);
-            lean_row_inv(L, L.tileA, y0, y31);
+            lean_pretwiddle<false, TW2_R>(L, U1, U1, v);
+            fft_col_lds<true, false, TWM_R>(L, v, L.tileA);
+            lean_row_inv<ROW_R>(L, L.tileA, y0, y31);
         }
         finish_pair(2, y0, y31);
         LEAN_MARK();

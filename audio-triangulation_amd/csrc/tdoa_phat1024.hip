@@ -280,41 +280,152 @@ struct Lane {
     const char *win;  // [w] (W[2w], W[2w+1]) / 128
 };
 
+// How far ahead of their use the transforms request table and tile values from
+// LDS, per call site: the kernel's register peak (pair (0,1), and mic 2 + cross:
+// two unit spectra and a working column live) keeps the lean forms, the four
+// other transforms (mic 0, mic 1, pairs (0,2) and (1,2): "roomy", 100+ free
+// registers) may take the deep ones.  Loads and waits only: no floating-point
+// operation, operand or association differs between the forms, so neither does
+// any output byte (tests/test_gpu_p1k_parent_bytes.py).  A/B variants; the
+// defaults are the forms that won on their own (DESIGN.md "k_p1k_lean" and
+// "Measured negative results (LDS read depths)", profiles/c2_lds_inflight_ab.txt;
+// us per 4096 frames on two step streams against 25.13 with every knob off).
+// P1K_TWM_ROOMY / P1K_TWM_TIGHT: fft_col_lds's W_1024 twiddles.
+//   8: groups of 8 after the DFT-32, each read next to its multiplies;
+//   4: groups of 4 in two register sets, group g + 1 requested ahead of group
+//      g's multiplies (the registers of 8);
+//  32: all of them requested ahead of the DFT-32 (62 more live registers).
+// Neither moved the step time: ROOMY=32 25.15, TIGHT=4 25.15
+#ifndef P1K_TWM_ROOMY
+#define P1K_TWM_ROOMY 8
+#endif
+#ifndef P1K_TWM_TIGHT
+#define P1K_TWM_TIGHT 8
+#endif
+// P1K_TW2_ROOMY / P1K_TW2_TIGHT: the W_2048 twiddles of a split or pre-twiddle.
+//   1: requested one bin pair ahead in the source (P1K_TWPF) -- the scheduler
+//      sinks each read to the end of that pair's arithmetic, a few
+//      instructions ahead of its use;
+//   2: the same, the read held ahead of that pair's arithmetic (the pair's
+//      first operand passes through an empty volatile asm behind the read),
+//      so the wait ahead of a pair leaves the next pair's read in flight
+//      (same registers);
+//  16: (roomy only) all requested at once -- a split's with its row reads, a
+//      pre-twiddle's ahead of its first pair (32 more live registers).
+// ROOMY=16: 24.67, every round a win; ROOMY=2 (with TIGHT=2) 24.89; TIGHT=2 alone 25.02
+#ifndef P1K_TW2_ROOMY
+#define P1K_TW2_ROOMY 16
+#endif
+#ifndef P1K_TW2_TIGHT
+#define P1K_TW2_TIGHT 1
+#endif
+// P1K_PRIOR_AHEAD=1: finish_pair requests its four lag-prior values at once,
+//   unconditionally (a clamped index), instead of one round trip each inside
+//   the candidates' exec-masked branches (24.74 against 25.13)
+#ifndef P1K_PRIOR_AHEAD
+#define P1K_PRIOR_AHEAD 1
+#endif
+// P1K_ROW_ROOMY: lean_row_inv's tile row.  16: two groups of 16 values; 32:
+//   the whole row requested at once, summed in the same two groups
+//   (24.97: inside the runs' spread of 0.30)
+#ifndef P1K_ROW_ROOMY
+#define P1K_ROW_ROOMY 16
+#endif
+// k_p1k_pcm16 (at 256 registers in the lean forms) may take smaller depths
+#ifndef P1K_TWM_ROOMY_PCM16
+#define P1K_TWM_ROOMY_PCM16 P1K_TWM_ROOMY
+#endif
+#ifndef P1K_TWM_TIGHT_PCM16
+#define P1K_TWM_TIGHT_PCM16 P1K_TWM_TIGHT
+#endif
+#ifndef P1K_TW2_ROOMY_PCM16
+#define P1K_TW2_ROOMY_PCM16 P1K_TW2_ROOMY
+#endif
+#ifndef P1K_TW2_TIGHT_PCM16
+#define P1K_TW2_TIGHT_PCM16 P1K_TW2_TIGHT
+#endif
+#ifndef P1K_ROW_ROOMY_PCM16
+#define P1K_ROW_ROOMY_PCM16 P1K_ROW_ROOMY
+#endif
+
 // first half of a 32 x 32 FFT_1024 on a residue column: DFT-32 in registers,
 // twiddle W_1024^{-+res k}, column write into the tile
-// ... with the twiddles read from LDS in groups of 8 ahead of their writes
-// (register-lean form for two waves per SIMD)
-template <bool INV, bool HALF_ZERO>
+// ... with the twiddles read from LDS ahead of their writes, DEPTH at a time
+// (P1K_TWM_*; 8 is the register-lean form for two waves per SIMD)
+template <bool INV, bool HALF_ZERO, int DEPTH>
 __device__ __forceinline__ void fft_col_lds(const Lane &L, f2 (&v)[32], char *tile)
 {
-    fft32d<INV, HALF_ZERO>(v);
-    wave_lds_sync();  // after the previous pass's row reads of this tile
-    const int wo = 8 * L.cs;
+    static_assert(DEPTH == 4 || DEPTH == 8 || DEPTH == 32, "fft_col_lds: twiddles 4, 8 or 32 ahead");
+    auto put = [&](int wo, int k, f2 w) {
+        f2 x = v[k];
+        if (k)
+            x = INV ? c_mulconj(x, w) : c_mul(x, w);
+        sts_f2(tile, wo + P1K_ROW * slot(k), x);
+    };
+    if constexpr (DEPTH == 32) {
+        // the table depends on the lane alone: requested here, its round trip
+        // passes under the DFT-32 (k = 0 is W = 1: not read)
+        const int wo = 8 * L.cs;
+        f2 tw[32];
 #pragma unroll
-    for (int k0 = 0; k0 < 32; k0 += 8) {
-        f2 tw[8];
+        for (int k = 1; k < 32; k++)
+            tw[k] = lds_f2(L.twm, wo + 256 * k);
+        __builtin_amdgcn_sched_barrier(0);  // (the scheduler would sink the reads to their uses)
+        fft32d<INV, HALF_ZERO>(v);
+        wave_lds_sync();  // after the previous pass's row reads of this tile
 #pragma unroll
-        for (int i = 0; i < 8; i++)
-            tw[i] = lds_f2(L.twm, wo + 256 * (k0 + i));
+        for (int k = 0; k < 32; k++)
+            put(wo, k, tw[k]);
+    } else if constexpr (DEPTH == 4) {
+        fft32d<INV, HALF_ZERO>(v);
+        wave_lds_sync();  // after the previous pass's row reads of this tile
+        const int wo = 8 * L.cs;
+        f2 tw[2][4];
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-            const int k = k0 + i;
-            f2 x = v[k];
-            if (k)
-                x = INV ? c_mulconj(x, tw[i]) : c_mul(x, tw[i]);
-            sts_f2(tile, wo + P1K_ROW * slot(k), x);
+        for (int i = 0; i < 4; i++)
+            tw[0][i] = lds_f2(L.twm, wo + 256 * i);
+#pragma unroll
+        for (int g = 0; g < 8; g++) {
+            if (g < 7) {
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    tw[(g + 1) & 1][i] = lds_f2(L.twm, wo + 256 * (4 * g + 4 + i));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+                put(wo, 4 * g + i, tw[g & 1][i]);
+        }
+    } else {
+        fft32d<INV, HALF_ZERO>(v);
+        wave_lds_sync();  // after the previous pass's row reads of this tile
+        const int wo = 8 * L.cs;
+#pragma unroll
+        for (int k0 = 0; k0 < 32; k0 += 8) {
+            f2 tw[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                tw[i] = lds_f2(L.twm, wo + 256 * (k0 + i));
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                put(wo, k0 + i, tw[i]);
         }
     }
     wave_lds_sync();  // before the row reads of other lanes' columns
 }
+struct NoHook {
+    __device__ void operator()() const {}
+};
 // second half: row read (row res) + forward DFT-32 -> V[k2] = Z[res + 32 k2]
-__device__ __forceinline__ void fft_row_fwd(const Lane &L, const char *tile, f2 (&V)[33])
+// (after_rows: further reads to request behind the row's, ahead of the DFT-32)
+template <typename Hook = NoHook>
+__device__ __forceinline__ void fft_row_fwd(const Lane &L, const char *tile, f2 (&V)[33], Hook after_rows = Hook())
 {
     f2 v[32];
     const int ro = P1K_ROW * L.cs;
 #pragma unroll
     for (int n = 0; n < 32; n++)
         v[n] = lds_f2(tile, ro + 8 * slot(n));
+    after_rows();
     fft32d<false, false>(v);
 #pragma unroll
     for (int k = 0; k < 32; k++)
@@ -343,10 +454,6 @@ namespace {
 
 // front end + forward FFT_1024 of one mic row, then the partner swap: V[k],
 // V[31 - k] hold Z[b], Z[N - b] (paired layout); V[32] = unit X[512] (lane 0)
-struct NoHook {
-    __device__ void operator()() const {}
-};
-
 // A row's words: the frame words w, and -- where the window is not in LDS
 // (WQ, the 4-wave workgroup) -- the window's Q15 tap pairs q from kp.window:
 // dword res + 32 t of either array covers samples 2 (res + 32 t), + 1.
@@ -355,9 +462,11 @@ struct NoHook {
 // sign-extended half-word minus off (no wrap, |y| <= 65535), one 24-bit
 // integer multiply by the tap (|y W| < 2^31), an arithmetic shift by 15 and a
 // convert (|s| <= 65535, exact) -- the units of the 8-bit form's floor(s W / 128).
-template <bool PCM16, int NQ, typename Hook = NoHook>
+// TWM: fft_col_lds's depth at this call site; after_rows: fft_row_fwd's hook
+template <bool PCM16, int TWM, int NQ, typename Hook = NoHook, typename Hook2 = NoHook>
 __device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
-                                              f2 (&V)[33], float e2, Hook after_front = Hook())
+                                              f2 (&V)[33], float e2, Hook after_front = Hook(),
+                                              Hook2 after_rows = Hook2())
 {
     constexpr bool WQ = NQ == 16;
     static_assert(!PCM16 || WQ, "the PCM16 front end reads the Q15 taps");
@@ -400,7 +509,7 @@ __device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)
         }
     }
     after_front();  // the row's words are consumed
-    fft_col_lds<false, true>(L, v, L.tileA);
+    fft_col_lds<false, true, TWM>(L, v, L.tileA);
     // X[512] = conj(Z[512]) is in units of X where every other bin holds 2 X
     // (the split's e, od), so its floor is e2 / 4.  One v_ldexp per row, issued
     // here under the transpose's LDS round trip (volatile: computed once per
@@ -409,7 +518,7 @@ __device__ __forceinline__ void lean_spectrum(const Lane &L, const uint32_t (&w)
     // 27.01 without it)
     float e2q;
     asm volatile("v_ldexp_f32 %0, %1, -2" : "=v"(e2q) : "s"(e2));
-    fft_row_fwd(L, L.tileA, V);
+    fft_row_fwd(L, L.tileA, V, after_rows);
     V[32] = c_unit(conjf2(V[16]), e2q);
     swap_upper_exec<true>(V, f2{0.0f, 0.0f});
 }
@@ -431,6 +540,18 @@ __device__ __forceinline__ void lean_split_w(f2 A, f2 Bv, f2 wk, float e2, f2 &u
 #define P1K_TWPF 5  // bit 0: lean_forward, 1: lean_forward_cross, 2: lean_pretwiddle
 #endif
 __device__ __forceinline__ f2 lean_tw2(const Lane &L, int k) { return lds_f2(L.tw2, 8 * L.cs + 256 * k); }
+// ... the next pair's, requested here and (TW2 = 2) kept here: `first`, an
+// operand of everything the current pair computes, is pinned behind the read
+// (volatile accesses and volatile asm keep their order; the packed operations
+// are plain asm, which the instruction selection otherwise places ahead of it)
+template <int TW2>
+__device__ __forceinline__ f2 lean_tw2_next(const Lane &L, int k, f2 &first)
+{
+    const f2 w = lean_tw2(L, k);
+    if constexpr (TW2 == 2)
+        pin(first);
+    return w;
+}
 __device__ __forceinline__ void lean_split(const Lane &L, f2 A, f2 Bv, int k, float e2, f2 &ub,
                                            f2 &un)
 {
@@ -438,18 +559,34 @@ __device__ __forceinline__ void lean_split(const Lane &L, f2 A, f2 Bv, int k, fl
 }
 
 // unit spectrum of one mic row, in place (paired layout)
-template <bool PCM16, int NQ, typename Hook = NoHook>
+// (TWM, TW2: the depths of the column pass's and the split's twiddle reads)
+template <bool PCM16, int TWM, int TW2, int NQ, typename Hook = NoHook>
 __device__ __forceinline__ void lean_forward(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
                                              f2 (&U)[33], float e2, Hook after_front = Hook())
 {
-    lean_spectrum<PCM16>(L, w, wq, U, e2, after_front);
+    static_assert(TW2 == 1 || TW2 == 2 || TW2 == 16, "lean_forward: split twiddles one pair ahead or all 16");
+    if constexpr (TW2 == 16) {
+        // the split's 16 twiddles requested behind the row reads: their round
+        // trip passes under the row's DFT-32
+        f2 t2[16];
+        lean_spectrum<PCM16, TWM>(L, w, wq, U, e2, after_front, [&] {
+#pragma unroll
+            for (int k = 0; k < 16; k++)
+                t2[k] = lean_tw2(L, k);
+        });
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            lean_split_w(U[k], U[31 - k], t2[k], e2, U[k], U[31 - k]);
+        return;
+    }
+    lean_spectrum<PCM16, TWM>(L, w, wq, U, e2, after_front);
 #if P1K_TWPF & 1
     f2 wn = lean_tw2(L, 0);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         const f2 wk = wn;
         if (k < 15)
-            wn = lean_tw2(L, k + 1);
+            wn = lean_tw2_next<TW2>(L, k + 1, U[k]);
         lean_split_w(U[k], U[31 - k], wk, e2, U[k], U[31 - k]);
     }
 #else
@@ -461,28 +598,29 @@ __device__ __forceinline__ void lean_forward(const Lane &L, const uint32_t (&w)[
 
 // unit spectrum V of one mic row consumed bin pair by bin pair as it is
 // produced: A <- conj(A) V, B <- conj(B) V (V is never whole after the split)
-template <bool PCM16, int NQ>
+template <bool PCM16, int TWM, int TW2, int NQ>
 __device__ __forceinline__ void lean_forward_cross(const Lane &L, const uint32_t (&w)[16], const uint32_t (&wq)[NQ],
                                                    f2 (&A)[33], f2 (&Bs)[33], float e2)
 {
     f2 V[33];
-    lean_spectrum<PCM16>(L, w, wq, V, e2);
+    lean_spectrum<PCM16, TWM>(L, w, wq, V, e2);
     A[32] = c_conjmul(A[32], V[32]);
     Bs[32] = c_conjmul(Bs[32], V[32]);
-#if P1K_TWPF & 2
-    f2 wn = lean_tw2(L, 0);
-#endif
+    // (TW2 = 2 requests one pair ahead here whatever P1K_TWPF says)
+    constexpr bool AHEAD = (P1K_TWPF & 2) || TW2 == 2;
+    [[maybe_unused]] f2 wn;
+    if constexpr (AHEAD)
+        wn = lean_tw2(L, 0);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         f2 ub, un;
-#if P1K_TWPF & 2
-        const f2 wk = wn;
-        if (k < 15)
-            wn = lean_tw2(L, k + 1);
-        lean_split_w(V[k], V[31 - k], wk, e2, ub, un);
-#else
-        lean_split(L, V[k], V[31 - k], k, e2, ub, un);
-#endif
+        if constexpr (AHEAD) {
+            const f2 wk = wn;
+            if (k < 15)
+                wn = lean_tw2_next<TW2>(L, k + 1, V[k]);
+            lean_split_w(V[k], V[31 - k], wk, e2, ub, un);
+        } else
+            lean_split(L, V[k], V[31 - k], k, e2, ub, un);
         A[k] = c_conjmul(A[k], ub);
         A[31 - k] = c_conjmul(A[31 - k], un);
         Bs[k] = c_conjmul(Bs[k], ub);
@@ -506,17 +644,31 @@ __device__ __forceinline__ f2 cmac_fwd(f2 acc, f2 d, int k)
 // pairs, so at most half a row of tile values is in registers at a time:
 // y0 = sum of the row, y31 = sum_i (v_i - v_{i+16}) W_32^i accumulated by
 // FMA in two chains per group
+// (DEPTH 32, P1K_ROW_ROOMY: both groups' tile values requested at once -- one
+// LDS round trip instead of two; the groups' sums are the same)
+template <int DEPTH>
 __device__ __forceinline__ void lean_row_inv(const Lane &L, const char *tile, f2 &y0, f2 &y31)
 {
+    static_assert(DEPTH == 16 || DEPTH == 32, "lean_row_inv: half a row or the whole row at once");
     const int ro = P1K_ROW * L.cs;
     f2 ga[2], gd[2];
+    [[maybe_unused]] f2 rv[2][8], ru[2][8];
+    if constexpr (DEPTH == 32) {
+#pragma unroll
+        for (int g = 0; g < 2; g++)
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                rv[g][i] = lds_f2(tile, ro + 8 * slot(8 * g + i));
+                ru[g][i] = lds_f2(tile, ro + 8 * slot(8 * g + i + 16));
+            }
+    }
 #pragma unroll
     for (int g = 0; g < 2; g++) {
         f2 a[8], c[2];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
-            const f2 v = lds_f2(tile, ro + 8 * slot(8 * g + i));
-            const f2 u = lds_f2(tile, ro + 8 * slot(8 * g + i + 16));
+            const f2 v = DEPTH == 32 ? rv[g][i] : lds_f2(tile, ro + 8 * slot(8 * g + i));
+            const f2 u = DEPTH == 32 ? ru[g][i] : lds_f2(tile, ro + 8 * slot(8 * g + i + 16));
             a[i] = v + u;
             const f2 d = v - u;
             c[i & 1] = i < 2 ? tw_only<false>(d, 8 * g + i) : cmac_fwd(c[i & 1], d, 8 * g + i);
@@ -555,24 +707,39 @@ __device__ __forceinline__ int fresh_tid()
 
 // packed inverse input of the cross spectrum R (paired layout; R[k] =
 // conj(A[k]) B[k] when B is given, else R = A), back in residue columns
-template <bool CROSS>
+// (TW2 16, P1K_TW2_ROOMY: the 16 twiddles requested at once ahead of the first pair)
+template <bool CROSS, int TW2>
 __device__ __forceinline__ void lean_pretwiddle(const Lane &L, const f2 (&A)[33], const f2 (&Bs)[33],
                                                 f2 (&v)[32])
 {
+    static_assert(TW2 == 1 || TW2 == 2 || TW2 == 16, "lean_pretwiddle: twiddles one pair ahead or all 16");
+    [[maybe_unused]] f2 t2[16];
+    if constexpr (TW2 == 16) {
+#pragma unroll
+        for (int k = 0; k < 16; k++)
+            t2[k] = lean_tw2(L, k);
+    }
 #if P1K_TWPF & 4
-    f2 wn = lean_tw2(L, 0);
+    [[maybe_unused]] f2 wn;
+    if constexpr (TW2 != 16)
+        wn = lean_tw2(L, 0);
 #endif
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        const f2 Rk = CROSS ? c_conjmul(A[k], Bs[k]) : A[k];
+        f2 Rk = CROSS ? c_conjmul(A[k], Bs[k]) : A[k];
         const f2 Rn = CROSS ? c_conjmul(A[31 - k], Bs[31 - k]) : A[31 - k];
+        f2 wk;
+        if constexpr (TW2 == 16)
+            wk = t2[k];
+        else {
 #if P1K_TWPF & 4
-        const f2 wk = wn;
-        if (k < 15)
-            wn = lean_tw2(L, k + 1);
+            wk = wn;
+            if (k < 15)
+                wn = lean_tw2_next<TW2>(L, k + 1, Rk);
 #else
-        const f2 wk = lean_tw2(L, k);
+            wk = lean_tw2(L, k);
 #endif
+        }
         const f2 s = c_addconj(Rk, Rn);
         const f2 q = c_mulconj(c_subconj(Rk, Rn), wk);
         v[k] = c_add_i(s, q);

@@ -2,6 +2,7 @@
 """Static opcode-class histogram of one kernel, per phase.  Diagnostic only.
 
     python3 tools/isa_hist.py kernel.s <mangled-name> [--split s_memtime]
+    python3 tools/isa_hist.py kernel.s <mangled-name> --waits
 
 Phases are the stretches between consecutive occurrences of the split
 instruction (the diagnostic build's phase stamps), so the same source built
@@ -68,8 +69,38 @@ def kernel_lines(path, name):
     return out
 
 
+def lds_waits(insts, near=20):
+    """Static LDS wait counts of one kernel: the LDS reads, the s_waitcnt that
+    name lgkmcnt, those that drain it (lgkmcnt(0)), and those within `near`
+    instructions of the most recent LDS read (a wait that close to a read has
+    little to hide the read's round trip under, unless its count leaves that
+    read in flight)."""
+    reads = waits = drains = close = drains_close = 0
+    last = None
+    for i, s in enumerate(insts):
+        op = s.split()[0]
+        if re.match(r"^ds_(read|load)", op):
+            reads += 1
+            last = i
+        elif op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", s)
+            if not m:
+                continue
+            waits += 1
+            zero = int(m.group(1)) == 0
+            drains += zero
+            if last is not None and i - last <= near:
+                close += 1
+                drains_close += zero
+    return {"lds_reads": reads, "lgkmcnt_waits": waits, "full_drains": drains, f"waits_within_{near}": close,
+            f"drains_within_{near}": drains_close}
+
+
 def main():
     path, name = sys.argv[1], sys.argv[2]
+    if "--waits" in sys.argv:  # the static LDS wait counts alone, one line
+        print(name, " ".join(f"{k} {v}" for k, v in lds_waits(kernel_lines(path, name)).items()))
+        return
     split = "s_memtime"
     if "--split" in sys.argv:
         split = sys.argv[sys.argv.index("--split") + 1]
